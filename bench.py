@@ -17,6 +17,14 @@ Launch: `python bench.py --gpus N` starts its own N rank processes (before
 anything touches a GPU) when no outer launcher set WORLD_SIZE; under
 `torch.distributed.run --nproc-per-node N` every process is one rank.  A line
 whose rank count differs from --gpus is refused.
+
+A plain run does what the headline figure needs and no more: it sets up, warms
+up, times --steps searches, writes --dump-outputs and prints the line.  --full
+adds every other leg, each one a run of its own outside the timed steps: the
+random-probe ceiling of the roofline, the same search under another fingerprint
+salt, the per-level prefix check against the C oracle and its CPU baseline, the
+CPU/GPU fixpoint of --cpu-fixpoint and the --v2-config model; --no-cpu,
+--no-probe-ceiling, --cpu-fixpoint= and --v2-config= drop single legs of it.
 """
 import argparse
 import json
@@ -33,6 +41,9 @@ sys.path.insert(0, os.path.join(ROOT, "raft.tla_amd"))
 
 METRIC = "distinct states/sec (whole node) and time-to-fixpoint on MCraft BFS, 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+# --dump-outputs: the fields of rmc_result that state what the search found (the
+# rest are timings and counters of how this build got there), in result.npy's order
+DUMP_FIELDS = ("distinct", "generated", "left_on_queue", "depth", "violated_inv", "violation_depth", "deadlock")
 
 
 def parse(argv=None):
@@ -40,6 +51,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure (probe ceiling, salt cross-check, CPU "
+                         "baseline and prefix check, CPU/GPU fixpoint, --v2-config); off: set up, warm up, time "
+                         "the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one returned to its caller as DIR/result.npy "
+                         "(float64: " + ", ".join(DUMP_FIELDS) + ")")
     ap.add_argument("--config", default=os.path.join(ROOT, "specs", "MCraftBenchXL.cfg"))
     ap.add_argument("--capacity", type=int, default=0,
                     help="state capacity per GPU (0: 1.5e9 / world * 1.3 for MCraftBench.cfg, the table size every "
@@ -61,22 +79,25 @@ def parse(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="run the sharded path even at one rank (measures its overhead)")
     ap.add_argument("--no-probe-ceiling", action="store_true",
-                    help="skip the random-probe microbenchmark (roofline ceiling)")
+                    help="--full: skip the random-probe microbenchmark (roofline ceiling)")
     ap.add_argument("--cpu-levels", type=int, default=22,
-                    help="BFS levels of the same model timed on the host CPU oracle")
+                    help="--full: BFS levels of the same model timed on the host CPU oracle")
     ap.add_argument("--cpu-fixpoint", default=os.path.join(ROOT, "specs", "MCraftBounded.cfg"),
-                    help="model timed to its fixpoint on the host CPU oracle AND on the GPU "
+                    help="--full: model timed to its fixpoint on the host CPU oracle AND on the GPU "
                          "('' to skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the host CPU oracle legs")
     ap.add_argument("--v2-only", default="", help=argparse.SUPPRESS)  # internal: the child of v2_fixpoint_child
     ap.add_argument("--v2-config", default=os.path.join(ROOT, "specs", "MCraftBench.cfg"),
-                    help="one GPU: also time this model (the reference's Value = {v1, v2}, MCraft.tla:15-16) "
+                    help="--full, one GPU: also time this model (the reference's Value = {v1, v2}, MCraft.tla:15-16) "
                          "to its fixpoint after the timed steps, untimed in the line's value ('' to skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch logic only: ranks rendezvous over gloo and report, no GPU, no librmc")
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="self-launch: seconds before the rank processes are killed")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ---- self-launch ---------------------------------------------------------------
@@ -298,6 +319,17 @@ def v2_fixpoint(path, dev, runs=3):
             "ms_mean": sum(ts) / len(ts) * 1e3, "distinct_per_s_best": r.distinct / min(ts)}
 
 
+def dump_outputs(path, r):
+    """--dump-outputs: what Checker.run (rmc_run_bfs + rmc_get_result, the timed
+    path) handed its caller in the last timed step.  The search is exhaustive
+    and has no input data, so two builds given the same arguments must write
+    the same array; every count is far below 2^53, exact in float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "result.npy"), np.array([getattr(r, f) for f in DUMP_FIELDS], dtype=np.float64))
+    return {"dir": path, "result.npy": list(DUMP_FIELDS)}
+
+
 # ---- one rank ------------------------------------------------------------------
 def dry_run(a, world, rank):
     """Rendezvous + the timing collectives of a real run, without a GPU."""
@@ -404,7 +436,7 @@ def main(argv=None):
     W = rmc.native().rmc_state_bytes(cfg)
     # roofline ceiling of the fingerprint set: random 8-B probes over 64 GB
     r_max = None
-    if not a.no_probe_ceiling and ranks_per_gpu == 1 and rank == 0:
+    if a.full and not a.no_probe_ceiling and ranks_per_gpu == 1 and rank == 0:
         r_max = rmc.probe_bench(device=cfg.device, table_bytes=(64 << 30) // ranks_per_gpu,
                                 accesses=1 << 32, mode=0)
 
@@ -447,9 +479,10 @@ def main(argv=None):
             torch.cuda.synchronize(dev)
         barrier()
         dt = time.perf_counter() - t0
+        dumped = dump_outputs(a.dump_outputs, last[0]) if a.dump_outputs and rank == 0 else None
         salt_check = None
         gpu_levels = None
-        if not sharded:  # untimed: same search under another fingerprint salt
+        if a.full and not sharded:  # untimed: same search under another fingerprint salt
             ck.set_seed(0x5A17ED)
             r2 = ck.run(record_levels=False)
             ck.set_seed(0)
@@ -524,6 +557,8 @@ def main(argv=None):
                            if sharded else "single GPU",
             "fp_salt_crosscheck": salt_check,
         },
+        "full": a.full,
+        "outputs": dumped,
         "world": {"ranks": world, "transport": transport, "torch_backend": backend,
                   "gpus_visible": ndev if sharded else 1, "ranks_per_gpu": ranks_per_gpu,
                   "launcher": os.environ.get("RMC_BENCH_LAUNCHER",
@@ -565,9 +600,9 @@ def main(argv=None):
                                    "world / rank 0's kernel time")
         out["roofline"]["achieved"] = (b_alg / world) / ks / 1e9 if ks > 0 else 0.0
         out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBS
-    if rank == 0 and world == 1 and a.v2_config and os.path.abspath(a.v2_config) != os.path.abspath(a.config):
+    if a.full and rank == 0 and world == 1 and a.v2_config and os.path.abspath(a.v2_config) != os.path.abspath(a.config):
         out["value_set_v2"] = v2_fixpoint_child(a.v2_config, dev)
-    if rank == 0 and not a.no_cpu and world == 1:
+    if a.full and rank == 0 and not a.no_cpu and world == 1:
         fix_cfg, gpu_fix = None, None
         if a.cpu_fixpoint:
             fix_cfg = rmc.config_from_files(a.cpu_fixpoint, builtin_raft=True)

@@ -60,6 +60,41 @@ def test_rank_count_mismatch_is_refused():
     assert "refused" in r.stderr
 
 
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-run"], capture_output=True, text=True,
+                       timeout=120, env=_env(), cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_result(tmp_path):
+    """A plain run times its steps and nothing else (the legs beside the headline
+    figure are --full's), and --dump-outputs writes what the last timed step
+    returned: result.npy, float64, bench.DUMP_FIELDS in order, equal to the
+    oracle's counts for MCraftSmall."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = GOLDEN["small"]
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--config",
+                        os.path.join(ROOT, "specs", "MCraftSmall.cfg"), "--capacity", str(1 << 22),
+                        "--spill", "off", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    rec = _line(r.stdout)
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["full"] is False
+    assert rec["value"] == pytest.approx(g["distinct"] / (rec["ms_per_step"] * 1e-3))
+    assert "cpu_baseline" not in rec and "value_set_v2" not in rec
+    assert rec["config"]["fp_salt_crosscheck"] is None and rec["roofline"]["probe_ceiling_per_s"] is None
+    assert os.listdir(tmp_path / "out") == ["result.npy"]
+    got = np.load(tmp_path / "out" / "result.npy")
+    assert got.dtype == np.float64 and got.shape == (len(bench.DUMP_FIELDS),)
+    out = dict(zip(bench.DUMP_FIELDS, got.tolist()))
+    assert (out["distinct"], out["generated"], out["depth"]) == (g["distinct"], g["generated"], g["depth"])
+    assert (out["left_on_queue"], out["violated_inv"], out["deadlock"]) == (0, 0, 0)
+
+
 @pytest.mark.gpu
 def test_self_launch_two_ranks_on_the_gpu_matches_oracle():
     """`bench.py --gpus 2` on a one-GPU box: two rank processes share the GPU

@@ -39,6 +39,20 @@ def load(path, **kw):
     return rmc.model_from_files(str(path), **kw)
 
 
+# Tests that edit only the model (specs/), never raft.tla, run everywhere: next
+# to the reference's raft.tla where it is on disk (the front-end verifies the
+# file), else against the compiled-in raft.tla.
+HAVE_REF = os.path.exists(REF_RAFT)
+
+
+def model_dir(tmp_path):
+    return workdir(tmp_path, raft=HAVE_REF)
+
+
+def load_model(path):
+    return load(path, builtin_raft=not HAVE_REF)
+
+
 SHIPPED = {
     "MCraftBounded": (3, 2, 2, 1, 2, 1, rmc.FLAG_CHECK_DEADLOCK, rmc.INV_TYPEOK),
     "MCraftBench": (3, 2, 2, 1, 3, 1, rmc.FLAG_CHECK_DEADLOCK, rmc.INV_TYPEOK),
@@ -109,20 +123,18 @@ def test_other_raft_tla_edits_are_refused_by_name(tmp_path, old, new, name):
         load(d / "MCraftBench.cfg")
 
 
-@need_ref
 def test_extra_constraint_conjunct_is_refused(tmp_path):
-    """The judge's /tmp/fe case: an extra conjunct in StateConstraint."""
-    d = workdir(tmp_path)
+    """An extra conjunct in StateConstraint."""
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace(
         "    /\\ \\A m \\in DOMAIN messages : messages[m] <= MaxDup\n",
         "    /\\ \\A m \\in DOMAIN messages : messages[m] <= MaxDup\n"
         "    /\\ \\A i \\in Server : commitIndex[i] = 0 /\\ state[i] /= Leader\n"))
     with pytest.raises(rmc.RmcError, match=r"StateConstraint: conjunct .*commitIndex"):
-        load(d / "MCraftBench.cfg")
+        load_model(d / "MCraftBench.cfg")
 
 
-@need_ref
 @pytest.mark.parametrize("body,msg", [
     ("~(\\A i \\in Server : currentTerm[i] <= MaxTerm)", "not a state bound"),
     ("\\/ \\A i \\in Server : currentTerm[i] <= MaxTerm\n    \\/ Cardinality(DOMAIN messages) <= MaxMsgs", "not a state bound"),
@@ -132,18 +144,17 @@ def test_extra_constraint_conjunct_is_refused(tmp_path):
     ("TRUE", "TRUE"),
 ])
 def test_constraint_forms_outside_the_bounds_are_refused(tmp_path, body, msg):
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace("StateConstraint ==\n", f"StateConstraint ==\n    {body}\nOldConstraint ==\n"))
     with pytest.raises(rmc.RmcError, match=msg):
-        load(d / "MCraftBench.cfg")
+        load_model(d / "MCraftBench.cfg")
 
 
-@need_ref
 def test_constraint_equivalent_forms_are_accepted(tmp_path):
     """Infix chains, references to other definitions and strict bounds map to
     the same bounds."""
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace("StateConstraint ==\n", (
         "TermBound == \\A s \\in Server : /\\ currentTerm[s] < MaxTerm + 0\n"
@@ -151,68 +162,64 @@ def test_constraint_equivalent_forms_are_accepted(tmp_path):
         "StateConstraint ==\n"
         "    TermBound /\\ Cardinality(BagToSet(messages)) <= MaxMsgs /\\ (\\A x \\in DOMAIN messages : messages[x] <= MaxDup)\n"
         "OldConstraint ==\n")).replace("MaxTerm + 0", "3"))
-    c = load(d / "MCraftBench.cfg")[0]
+    c = load_model(d / "MCraftBench.cfg")[0]
     assert (c.max_term, c.max_log_len, c.max_msgs, c.max_dup) == (2, 1, 3, 1)
 
 
-@need_ref
 @pytest.mark.parametrize("sym,ok", [("Permutations(Server)", True), ("Permutations(Servers3)", True),
                                     ("Permutations(Value)", False),
                                     ("Permutations(Server) \\cup Permutations(Value)", False)])
 def test_symmetry_must_be_server_permutations(tmp_path, sym, ok):
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace("ServerSymmetry == Permutations(Server)", f"ServerSymmetry == {sym}"))
     if ok:
-        assert load(d / "MCraftBoundedSym.cfg")[0].flags & rmc.FLAG_SYMMETRY
+        assert load_model(d / "MCraftBoundedSym.cfg")[0].flags & rmc.FLAG_SYMMETRY
     else:
         with pytest.raises(rmc.RmcError, match="SYMMETRY ServerSymmetry"):
-            load(d / "MCraftBoundedSym.cfg")
+            load_model(d / "MCraftBoundedSym.cfg")
 
 
-@need_ref
 def test_invariant_definitions_must_be_the_compiled_ones(tmp_path):
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     text = p.read_text()
     p.write_text(text.replace("currentTerm[i] = currentTerm[j]) => i = j", "currentTerm[i] = currentTerm[j]) => TRUE"))
     with pytest.raises(rmc.RmcError, match="INVARIANT OneLeaderPerTerm"):
-        load(d / "MCraftBug.cfg")
+        load_model(d / "MCraftBug.cfg")
     # a helper the invariant uses counts too (deep digest)
     p.write_text(text.replace("/\\ m.mterm <= currentTerm[m.msource]", "/\\ m.mterm >= 0"))
     with pytest.raises(rmc.RmcError, match="INVARIANT MessagesInv"):
-        load(d / "MCraftMessages.cfg")
+        load_model(d / "MCraftMessages.cfg")
     p.write_text(text.replace("IsPrefix(s, t) == Len(s) <= Len(t)", "IsPrefix(s, t) == Len(s) >= 0"))
     cfg = d / "MCraftMessages.cfg"
     cfg.write_text(cfg.read_text().replace("INVARIANT TypeOK MessagesInv", "INVARIANT LeaderCompleteness"))
     with pytest.raises(rmc.RmcError, match="INVARIANT LeaderCompleteness"):
-        load(cfg)
+        load_model(cfg)
     # raft.tla's proof invariants sit past its module end: the model must define them
     p.write_text(text.replace("LeaderCompleteness ==", "LeaderCompletenessX =="))
     with pytest.raises(rmc.RmcError, match="not defined by the model"):
-        load(cfg)
+        load_model(cfg)
 
 
-@need_ref
 def test_override_must_be_the_compiled_bug_variant(tmp_path):
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace("    /\\ votesGranted[i] /= {}\n", "    /\\ TRUE\n"))
     with pytest.raises(rmc.RmcError, match="BecomeLeader <- BugBecomeLeader"):
-        load(d / "MCraftBug.cfg")
+        load_model(d / "MCraftBug.cfg")
     cfg = d / "MCraftBounded.cfg"
     cfg.write_text(cfg.read_text() + "\nCONSTANT Timeout <- BugBecomeLeader\n")
     with pytest.raises(rmc.RmcError, match="Timeout"):
-        load(cfg)
+        load_model(cfg)
 
 
-@need_ref
 def test_model_may_not_redefine_raft_operators(tmp_path):
-    d = workdir(tmp_path)
+    d = model_dir(tmp_path)
     p = d / "MCraftBounded.tla"
     p.write_text(p.read_text().replace("Values1 == {v1}", "Values1 == {v1}\nQuorum == {Server}"))
     with pytest.raises(rmc.RmcError, match="redefines raft.tla's Quorum"):
-        load(d / "MCraftBench.cfg")
+        load_model(d / "MCraftBench.cfg")
 
 
 def test_server_and_value_sets(tmp_path):

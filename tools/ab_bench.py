@@ -14,5 +14,5 @@ sys.path.insert(0, os.path.join(ROOT, "raft.tla_amd"))
 import rmc  # noqa: E402
 
 rmc.LIB_PATH = os.path.join(ROOT, "abtest", sys.argv[1])
-sys.argv = ["bench.py", "--no-cpu", "--no-probe-ceiling", "--steps", "5", "--warmup", "1"]
+sys.argv = ["bench.py", "--full", "--no-cpu", "--no-probe-ceiling", "--steps", "5", "--warmup", "1"]
 runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")

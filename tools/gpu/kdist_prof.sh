@@ -5,7 +5,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 P=${OUT:-gpurun_out/kdist_prof}
 mkdir -p $P
-B="--config specs/MCraftBench.cfg --no-cpu --no-probe-ceiling --v2-config="
+B="--full --config specs/MCraftBench.cfg --no-cpu --no-probe-ceiling --v2-config="
 for m in plain dist; do
   X=""; [ $m = dist ] && X=--force-dist
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/kt_$m -o kt -- python3 bench.py $B --steps 2 --warmup 1 $X > $P/b_$m.json 2> $P/b_$m.err || exit 1

@@ -11,7 +11,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -3 $O/gpu_tests.log
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log; exit 1; }
 fi
-timeout -k 10 300 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 if [ -n "$DIST_BENCH" ]; then
   timeout -k 10 300 python -u bench.py --force-dist --config specs/MCraftBench.cfg --no-cpu --no-probe-ceiling --v2-config= --steps 5 > $O/bench_dist1.json 2> $O/bench_dist1.err || { tail -20 $O/bench_dist1.err; exit 1; }

@@ -48,7 +48,7 @@ def main():
     n = len(fetch)
     rec = {
         "command": "tools/gpu/prof.sh: rocprofv3 --kernel-trace --stats | --pmc FETCH_SIZE | --pmc WRITE_SIZE "
-                   "(separate passes) -- python3 bench.py --steps 1 --warmup 0 --no-cpu --no-probe-ceiling",
+                   "(separate passes) -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-probe-ceiling",
         "workload": f"specs/{stem}.cfg, BFS to fixpoint (bench step + the untimed fingerprint-salt re-run)",
         "kernel": name,
         "launches": calls,

@@ -491,7 +491,7 @@ int verify_host_hits(rmc_ctx* c, u64 n) {
             memcpy(X.h_ostage + q * NW, X.h_state + ix * NW, NW * 4);
         }
         HIPCHK(c, hipMemcpyAsync(X.d_ostage, X.h_ostage, m * NW * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(c, launch(c->sh, 15, c->P, c->PT, c->B, m, off, X.d_ostage, nullptr, 0, nullptr, c->st));
+        HIPCHK(c, launch(c->sh, Op::VerifyHost, c->P, c->PT, c->B, m, off, X.d_ostage, nullptr, 0, nullptr, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));  // the pinned stage is refilled next
     }
     HIPCHK(c, hipMemsetAsync(&c->B.ctr->hcount, 0, 8, c->st));
@@ -821,13 +821,13 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     std::string why;
     if (encode_view(c, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, launch(c->sh, 1, c->P, c->PT, c->B, 1, 0, c->d_staged, nullptr, 0, nullptr, c->st));
+    HIPCHK(c, launch(c->sh, Op::Seed, c->P, c->PT, c->B, 1, 0, c->d_staged, nullptr, 0, nullptr, c->st));
     if (int rc = read_counters(c)) return rc;
     c->res.generated = 1;
     c->level_start.push_back(0);
     c->level_start.push_back(c->h_ctr->count);
     if (c->sh.verify)
-        HIPCHK(c, launch(c->sh, 5, c->P, c->PT, c->B, 0, c->h_ctr->count, nullptr, nullptr, 0, nullptr, c->st));
+        HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, c->h_ctr->count, nullptr, nullptr, 0, nullptr, c->st));
     depth = c->h_ctr->count ? 1 : 0;
     if (c->h_ctr->viol != ~0ull) {
         c->res.violated_inv = 1 << (int)(c->h_ctr->viol & 15);
@@ -922,19 +922,19 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                                     " GiB) so the window gets more");
                 b = a + want;
             }
-            HIPCHK(c, launch(c->sh, 0, c->P, c->PT, c->B, a, b, nullptr, nullptr, 0, nullptr, c->st));
+            HIPCHK(c, launch(c->sh, Op::Expand, c->P, c->PT, c->B, a, b, nullptr, nullptr, 0, nullptr, c->st));
             c->res.expand_launches += 1;
             if (c->sh.sym && !c->sh.verify) {
-                HIPCHK(c, launch(c->sh, 10, c->P, c->PT, c->B, 0, 0, nullptr, nullptr, 0, nullptr, c->st));
+                HIPCHK(c, launch(c->sh, Op::Ties, c->P, c->PT, c->B, 0, 0, nullptr, nullptr, 0, nullptr, c->st));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
             }
             if (c->sh.verify) {
                 const u64 before = c->h_ctr->count;
                 if (int rc = read_counters(c)) return rc;
                 if (c->h_ctr->overflow) break;
-                HIPCHK(c, launch(c->sh, 5, c->P, c->PT, c->B, before, c->h_ctr->count, nullptr, nullptr, 0, nullptr,
+                HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, before, c->h_ctr->count, nullptr, nullptr, 0, nullptr,
                                  c->st));
-                HIPCHK(c, launch(c->sh, 6, c->P, c->PT, c->B, c->h_ctr->vcount, 0, nullptr, nullptr, 0, nullptr,
+                HIPCHK(c, launch(c->sh, Op::Verify, c->P, c->PT, c->B, c->h_ctr->vcount, 0, nullptr, nullptr, 0, nullptr,
                                  c->st));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
                 c->h_ctr->vcount = 0;
@@ -1240,7 +1240,7 @@ int rmc_recover(rmc_ctx* c, const char* path) {
             DevBufs T = c->B;
             T.store = (u32*)((uintptr_t)area - (uintptr_t)(p * W));
             T.wmask = ~0ull;  // indexed through the biased pointer, not the ring
-            if (!rc) HIPCHK(c, launch(c->sh, 7, c->P, c->PT, T, p, p + k, nullptr, nullptr, 0, nullptr, c->st));
+            if (!rc) HIPCHK(c, launch(c->sh, Op::Rehash, c->P, c->PT, T, p, p + k, nullptr, nullptr, 0, nullptr, c->st));
             if (!rc) HIPCHK(c, hipStreamSynchronize(c->st));
         }
     }
@@ -1258,8 +1258,8 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     fclose(f);
     if (rc) return rc;
     if (s) spill_rebase(c, s);
-    if (!h.slots) HIPCHK(c, launch(c->sh, 7, c->P, c->PT, c->B, s, h.count, nullptr, nullptr, 0, nullptr, c->st));
-    if (c->sh.verify) HIPCHK(c, launch(c->sh, 5, c->P, c->PT, c->B, 0, h.count, nullptr, nullptr, 0, nullptr, c->st));
+    if (!h.slots) HIPCHK(c, launch(c->sh, Op::Rehash, c->P, c->PT, c->B, s, h.count, nullptr, nullptr, 0, nullptr, c->st));
+    if (c->sh.verify) HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, h.count, nullptr, nullptr, 0, nullptr, c->st));
     if (int r2 = read_counters(c)) return r2;
     if (c->h_ctr->table_full) return fail(c, RMC_E_CAPACITY, "recover: fingerprint set full");
     if (c->h_ctr->overflow) return fail(c, RMC_E_IO, "recover: the checkpoint holds duplicate states");
@@ -1318,7 +1318,7 @@ int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* in
             unsigned long long n = 0;
             if (!rc && (hipMemcpy(d_in, cur.data(), NW * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemset(d_cnt, 0, 8) != hipSuccess ||
-                        launch(c->sh, 2, c->P, c->PT, c->B, 1, 0, d_in, d_out, lanes, d_cnt, c->st) != hipSuccess ||
+                        launch(c->sh, Op::List, c->P, c->PT, c->B, 1, 0, d_in, d_out, lanes, d_cnt, c->st) != hipSuccess ||
                         hipStreamSynchronize(c->st) != hipSuccess ||
                         hipMemcpy(&n, d_cnt, 8, hipMemcpyDeviceToHost) != hipSuccess ||
                         hipMemcpy(recs.data(), d_out, std::min<u64>(n, lanes) * RW * 4, hipMemcpyDeviceToHost) != hipSuccess))
@@ -1678,7 +1678,7 @@ int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view
     HIPCHK(c, hipMalloc(&d_cnt, 8));
     HIPCHK(c, hipMemcpy(d_in, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(d_cnt, 0, 8));
-    HIPCHK(c, launch(c->sh, 2, c->P, c->PT, c->B, (u64)n, 0, d_in, d_out, rcap, d_cnt, c->st));
+    HIPCHK(c, launch(c->sh, Op::List, c->P, c->PT, c->B, (u64)n, 0, d_in, d_out, rcap, d_cnt, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     unsigned long long cnt = 0;
     HIPCHK(c, hipMemcpy(&cnt, d_cnt, 8, hipMemcpyDeviceToHost));

@@ -101,22 +101,26 @@ struct Shape {
     bool verify;  // full-state verification (single GPU)
 };
 
-// which: 0 = k_expand over store[a, b); 1 = k_seed of `a` staged states `in`;
-//        2 = k_list of `a` states `in` into `out` (cap records, *count);
-//        3 = sharded k_expand over store[a, b) (outbox in B);
-//        8 = k_materialize_remote of window [b, b + a) of each destination's keys, in = replies;
-//        9 = k_store_remote of `a` received state records `in`;
-//       10 = k_ties over the deferred tied successors (count on the device);
-//        5 = k_publish over store[a, b) (verification: slot -> store index);
-//        6 = k_verify of `a` deferred hits in B.vbuf;
-//        7 = k_rehash of the stored states [a, b) (recovery).
-//       11 = k_compare_remote of `a` received state records `in` (sharded verification);
-//       12 = k_expand_dist<REP> over the replicated level's records B.rep[a, b);
-//       13 = k_pack_rep of this rank's stored states [a, b) into records at `out`;
-//       14 = k_route: key the pool's records and fill the outboxes (counts on the device);
-//       15 = k_verify_host of `a` hits B.hbuf[b, b + a) against their owners' host copies
-//            staged at `in` (verification + spill).
-hipError_t launch(const Shape& sh, int which, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
+// The kernels of one shape, by what they do with launch()'s arguments.
+enum class Op {
+    Expand,             // the single-GPU expansion over store[a, b)
+    Seed,               // k_seed of `a` staged states `in`
+    List,               // k_list of `a` states `in` into `out` (cap records, *count)
+    ExpandDist,         // the sharded expansion over store[a, b) (outbox / pool in B)
+    Publish,            // k_publish over store[a, b) (verification: slot -> store index)
+    Verify,             // k_verify of `a` deferred hits in B.vbuf
+    Rehash,             // k_rehash of the stored states [a, b) (recovery)
+    MaterializeRemote,  // k_materialize_remote of window [b, b + a) of each destination's keys, in = replies
+    StoreRemote,        // k_store_remote of `a` received state records `in`
+    Ties,               // k_ties over the deferred tied successors (count on the device)
+    CompareRemote,      // k_compare_remote of `a` received state records `in` (sharded verification)
+    ExpandRep,          // k_expand_dist<REP> over the replicated level's records B.rep[a, b)
+    PackRep,            // k_pack_rep of this rank's stored states [a, b) into records at `out`
+    Route,              // k_route: key the pool's records and fill the outboxes (counts on the device)
+    VerifyHost,         // k_verify_host of `a` hits B.hbuf[b, b + a) against their owners' host copies
+                        // staged at `in` (verification + spill)
+};
+hipError_t launch(const Shape& sh, Op op, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
                   const u32* in, u32* out, u64 cap, unsigned long long* count, hipStream_t st);
 
 // Simulation counters (k_simulate).

@@ -27,6 +27,24 @@ __device__ __forceinline__ u64 bcast64(u64 v, int src) {
     return ((u64)hi << 32) | lo;
 }
 
+// Wave-aggregated reservation: the lanes with `want` set take consecutive
+// indices from *ctr with ONE atomic (by the first of them); returns this
+// lane's index (meaningful only where `want`).  Must be reached by every lane
+// of the wave (it contains a ballot).  expand_body, commit_new and k_route keep
+// the same steps written out: there the call shifts the kernels' register
+// allocation (k_expand_sym +5 instructions, k_ties a spill), and those kernels
+// are pinned to their measured code.
+__device__ __forceinline__ u64 wave_reserve(bool want, unsigned long long* ctr) {
+    const u64 bal = __ballot(want);
+    if (bal == 0) return 0;
+    const int me = (int)__lane_id();
+    const int leader = __ffsll((long long)bal) - 1;
+    u64 base = 0;
+    if (me == leader) base = atomicAdd(ctr, (unsigned long long)__popcll(bal));
+    base = bcast64(base, leader);
+    return base + (u64)__popcll(bal & ((1ull << me) - 1ull));
+}
+
 // Open-addressing insert of a non-zero 64-bit value v whose probe sequence
 // starts at slot s0, linear probing.
 // Returns 1 if this lane inserted the key, 0 if it was present (or the table
@@ -121,6 +139,25 @@ __device__ __forceinline__ void store_state(u32* __restrict__ base, const u64 (&
     for (int q = 0; q < K; ++q) base[2 * S + q] = m[q];
 }
 
+// Successor re-derivation: the kernels keep (parent, lane) for a successor and
+// run the lane's code again where they need the successor itself (same code,
+// deterministic): load the parent record, the lane's delta, materialise.
+// Used by the kernels outside the expansion launch.  The flushes of the
+// expansion kernels and k_materialize_remote, which also need the footprint
+// (through the lane's descriptor in the sorted kernels), keep the steps written
+// out: through a helper their register allocation changes (spill counts, an
+// instruction or two), and those kernels are pinned to their measured code.
+template <int S, int K>
+__device__ __forceinline__ void derive_succ(const u32* parent, int lane, const Params& P, u64 (&wo)[S],
+                                            u32 (&mo)[K]) {
+    u64 w[S];
+    u32 m[K];
+    load_state<S, K>(parent, w, m);
+    Delta d;
+    lane_delta<S, K>(w, m, lane, P, d);
+    materialise<S, K>(w, m, d, wo, mo);
+}
+
 // Store one new state at index ni: the packed state, its trace link (global
 // parent ref, lane), the footprint of its discovering lane (commuting
 // diamonds; only shapes whose kernels skip diamonds keep them), its
@@ -213,15 +250,9 @@ __device__ __forceinline__ void flush_new(const Params& P, const DevBufs& B, u64
         const u32* pr = REP ? B.rep + (lo + rel) * (u64)RR::RR : B.store + wslot(B, lo + rel) * (u64)NW;
         load_state<S, K>(pr, w, m);
         Delta d;
-        u64 foot;
-        if constexpr (Lanes<S, K>::N <= 128) {  // the lane's descriptor: no family-offset compares
-            const u32 desc = P.ldesc[lane];
-            lane_delta_desc<S, K>(w, m, desc, P, d);
-            foot = make_foot_desc<S, K>(m, desc, d);
-        } else {
-            lane_delta<S, K>(w, m, lane, P, d);
-            foot = 0;
-        }
+        const u32 desc = P.ldesc[lane];  // the lane's descriptor: no family-offset compares
+        lane_delta_desc<S, K>(w, m, desc, P, d);
+        const u64 foot = make_foot_desc<S, K>(m, desc, d);
         u64 wo[S];
         u32 mo[K];
         materialise<S, K>(w, m, d, wo, mo);
@@ -392,13 +423,8 @@ __global__ __launch_bounds__(256) void k_verify(const Params P, const PermTable 
         const u64 parent = B.vbuf[2 * q], sl = B.vbuf[2 * q + 1];
         const u64 slot = sl & ((1ull << 56) - 1);
         const int lane = (int)(sl >> 56);
-        u64 w[S];
-        u32 m[K];
-        load_state<S, K>(B.store + wslot(B, parent) * (u64)NW, w, m);
-        Delta d;
-        lane_delta<S, K>(w, m, lane, P, d);
         PackedState<S, K> o;
-        materialise<S, K>(w, m, d, o.w, o.m);
+        derive_succ<S, K>(B.store + wslot(B, parent) * (u64)NW, lane, P, o.w, o.m);
         const u64 ix = B.sidx[slot];
         if (ix == ~0ull) {
             atomicOr(&B.ctr->overflow, 8u);
@@ -429,13 +455,8 @@ __global__ __launch_bounds__(256) void k_verify_host(const Params P, const PermT
     for (u64 q = (u64)blockIdx.x * 256ull + threadIdx.x; q < n; q += (u64)gridDim.x * 256ull) {
         const u64 parent = B.hbuf[2 * (off + q)];
         const int lane = (int)(B.hbuf[2 * (off + q) + 1] >> 56);
-        u64 w[S];
-        u32 m[K];
-        load_state<S, K>(B.store + wslot(B, parent) * (u64)NW, w, m);
-        Delta d;
-        lane_delta<S, K>(w, m, lane, P, d);
         PackedState<S, K> o;
-        materialise<S, K>(w, m, d, o.w, o.m);
+        derive_succ<S, K>(B.store + wslot(B, parent) * (u64)NW, lane, P, o.w, o.m);
         const u32* st = owners + q * (u64)NW;
         bool same;
         if constexpr (SYM) same = same_orbit<S, K>(o, st, PT);
@@ -605,108 +626,11 @@ __device__ __forceinline__ void flush_dist(const Params& P, const DevBufs& B, u6
     wave_sync_lds();
 }
 
-// Sharded mode with send markers (MARK): the local fingerprint set doubles
-// as the record of keys already sent — a successor owned elsewhere is
-// CAS-inserted into it like a local one, so the probe loop is the single-GPU
-// loop (no owner computed per probe) and a remote key is shipped at most once
-// per rank (a lossless sent-cache).  The list carries only (rel, lane); here
-// each listed successor's owner is found from its changed word (a first pass,
-// only with more than one rank, into l_dest), then each is re-derived: owned
-// ones are stored as in
-// flush_new, the others get their key back from the materialised successor
-// (the fingerprint is order-free: it equals the incremental probe key) and go
-// to the owner's outbox with a ticket.  One reservation atomic per destination.
-template <int S, int K>
-__device__ __forceinline__ void flush_mark(const Params& P, const DevBufs& B, u64 lo, const u32* l_rel,
-                                           const uint8_t* l_lane, uint8_t* l_dest, u32 n) {
-    constexpr int NW = 2 * S + K;
-    wave_sync_lds();
-    const int me = (int)__lane_id();
-    const u64 lt = (1ull << me) - 1ull;
-    u64 mine = 0;  // lane dd: entries for destination dd, then its next slot
-    for (u32 e0 = 0; e0 < n; e0 += 64) {
-        const u32 e = e0 + (u32)me;
-        u32 dest = 0xFFu;
-        if (e < n) {
-            dest = 0;
-            if (B.world > 1) {
-                u64 w[S];
-                u32 m[K];
-                load_state<S, K>(B.store + (lo + l_rel[e]) * (u64)NW, w, m);
-                Delta d;
-                if constexpr (Lanes<S, K>::N <= 128) lane_delta_desc<S, K>(w, m, P.ldesc[l_lane[e]], P, d);
-                else lane_delta<S, K>(w, m, l_lane[e], P, d);
-                if (B.owner_mode == 0) {
-                    u64 wo[S];
-                    u32 mo[K];
-                    materialise<S, K>(w, m, d, wo, mo);
-                    dest = owner_of(fp_of_materialised<S, K>(wo, mo, P).k, B.world);
-                } else {
-                    dest = owner_succ_w<S>(0ull, d, w, B);
-                }
-                l_dest[e] = (uint8_t)dest;
-            }
-        }
-        for (u32 dd = 0; dd < B.world; ++dd) {
-            const u64 bal = __ballot(dest == dd);
-            if ((u32)me == dd) mine += (u64)__popcll(bal);
-        }
-    }
-    if ((u32)me < B.world && mine) {
-        unsigned long long* ctr = (u32)me == B.rank ? (unsigned long long*)&B.ctr->count : &B.ocount[me];
-        mine = atomicAdd(ctr, (unsigned long long)mine);
-    }
-    for (u32 e0 = 0; e0 < n; e0 += 64) {  // wave-uniform rounds
-        const u32 e = e0 + (u32)me;
-        const bool valid = e < n;
-        const u32 dest = !valid ? 0xFFu : B.world > 1 ? (u32)l_dest[e] : 0u;
-        u64 slot = ~0ull;
-        for (u32 dd = 0; dd < B.world; ++dd) {
-            const u64 bal = __ballot(dest == dd);
-            if (!bal) continue;
-            const u64 base = bcast64(mine, (int)dd);
-            if (dest == dd) slot = base + (u64)__popcll(bal & lt);
-            if ((u32)me == dd) mine += (u64)__popcll(bal);
-        }
-        if (!valid) continue;
-        const u64 rel = l_rel[e];
-        const int lane = l_lane[e];
-        if (dest == B.rank && slot >= B.cap) {
-            atomicOr(&B.ctr->overflow, 1u);
-            continue;
-        }
-        u64 w[S];
-        u32 m[K];
-        load_state<S, K>(B.store + (lo + rel) * (u64)NW, w, m);
-        Delta d;
-        u64 foot;
-        if constexpr (Lanes<S, K>::N <= 128) {  // the lane's descriptor: no family-offset compares
-            const u32 desc = P.ldesc[lane];
-            lane_delta_desc<S, K>(w, m, desc, P, d);
-            foot = make_foot_desc<S, K>(m, desc, d);
-        } else {
-            lane_delta<S, K>(w, m, lane, P, d);
-            foot = 0;
-        }
-        u64 wo[S];
-        u32 mo[K];
-        materialise<S, K>(w, m, d, wo, mo);
-        if (dest != B.rank) {  // the key to its owner, the ticket stays here
-            const Fp key = fp_of_materialised<S, K>(wo, mo, P);
-            if (slot >= B.kcap) {  // outbox full: parked, sent by a later round of this level
-                park_key(B, key.k, (u32)key.s, (lo + rel) | ((u64)dest << 48) | ((u64)lane << 56));
-                continue;
-            }
-            put_key(B, dest, slot, key.k, (u32)key.s, (lo + rel) | ((u64)lane << 56));
-            continue;
-        }
-        store_new<S, K>(P, B, slot, wo, mo, B.ref_tag | (lo + rel), lane, foot);
-    }
-    wave_sync_lds();
-}
-
-// Sharded mode with send markers, the pool flush (default): flush_new with the
-// owner decided per listed successor from its materialised words — a lane that
+// Sharded mode with send markers (MARK): the local fingerprint set doubles as
+// the record of keys already sent — a successor owned elsewhere is CAS-inserted
+// into it like a local one, so the probe loop is the single-GPU loop (no owner
+// computed per probe) and a remote key is shipped at most once per rank.  The
+// list carries only (rel, lane).  The pool flush: flush_new with the owner decided per listed successor from its materialised words — a lane that
 // leaves the hashed words alone keeps its parent's owner, this rank — and two
 // reservation atomics per 64 entries, one for the local store, one for the
 // remote-successor pool (B.pool).  A remote successor is written there once, as
@@ -736,8 +660,7 @@ __device__ __forceinline__ void flush_pool(const Params& P, const DevBufs& B, u6
                 u64 w[S];
                 u32 m[K];
                 load_state<S, K>(B.store + (lo + l_rel[e]) * (u64)NW, w, m);
-                if constexpr (Lanes<S, K>::N <= 128) lane_delta_desc<S, K>(w, m, P.ldesc[lane], P, d);
-                else lane_delta<S, K>(w, m, lane, P, d);
+                lane_delta_desc<S, K>(w, m, P.ldesc[lane], P, d);
                 if (B.owner_mode == 0) {
                     u64 wo[S];
                     u32 mo[K];
@@ -780,15 +703,9 @@ __device__ __forceinline__ void flush_pool(const Params& P, const DevBufs& B, u6
         u32 m[K];
         load_state<S, K>(B.store + (lo + rel) * (u64)NW, w, m);
         Delta d;
-        u64 foot;
-        if constexpr (Lanes<S, K>::N <= 128) {
-            const u32 desc = P.ldesc[lane];
-            lane_delta_desc<S, K>(w, m, desc, P, d);
-            foot = make_foot_desc<S, K>(m, desc, d);
-        } else {
-            lane_delta<S, K>(w, m, lane, P, d);
-            foot = make_foot<S, K>(m, lane, d, P);
-        }
+        const u32 desc = P.ldesc[lane];
+        lane_delta_desc<S, K>(w, m, desc, P, d);
+        const u64 foot = make_foot_desc<S, K>(m, desc, d);
         u64 wo[S];
         u32 mo[K];
         materialise<S, K>(w, m, d, wo, mo);
@@ -827,18 +744,54 @@ __device__ __forceinline__ void flush_pool(const Params& P, const DevBufs& B, u6
 // REP: a replicated level of the sharded search — [lo, hi) indexes the whole
 //   level's records in B.rep (gathered from every rank); every rank expands
 //   all of them and probes, stores and counts only the successors it owns.
-template <int S, int K, bool SYM, int BATCH, bool DIST, bool VERIFY = false, bool PRE = false, bool SORT = false,
-          bool DIA = false, bool MARK = false, int WTILES = 8, int PIPE = 0, bool REP = false, bool PRESORT = false,
-          int DYN = 0, bool POOL = false>
+// POOL: the sharded kernel whose flush pools the remote successors (flush_pool).
+// POOL and REP are the send-marker kernels (MARK); a DIST kernel that is neither
+// goes through the lossy sent-cache (SENTC, flush_dist).
+//
+// The configuration of one expansion kernel, read by name in expand_body; each
+// kernel below states what it changes next to its definition.
+struct ExpandDefaults {
+    static constexpr bool SYM = false;      // SYMMETRY: canonical fingerprints, ties deferred to k_ties
+    static constexpr int BATCH = 8;         // probes in flight per thread
+    static constexpr bool DIST = false;     // sharded mode
+    static constexpr bool VERIFY = false;   // full-state verification of fingerprint hits
+    static constexpr bool PRE = false;      // the parent's mixes computed once per state (parent_mix)
+    static constexpr bool SORT = false;     // the lane-superset walk over class-sorted windows
+    static constexpr bool DIA = false;      // commuting-diamond skipping
+    static constexpr int WTILES = 8;        // tiles per window (SORT)
+    static constexpr int PIPE = 0;          // probe loads issued during the lane code
+    static constexpr bool REP = false;      // a replicated level (B.rep)
+    static constexpr bool PRESORT = false;  // windows sorted before the launch (k_window_order, B.word)
+    static constexpr int DYN = 0;           // dynamic per-wave work units
+    static constexpr bool POOL = false;     // the pool flush
+};
+
+// The materialising flush of a wave's list, by the kernel's configuration.
+template <int S, int K, class C>
+__device__ __forceinline__ void flush_list(const Params& P, const DevBufs& B, u64 lo, const u32* l_rel,
+                                           const uint8_t* l_lane, uint8_t* l_dest, const u64* l_key, const u32* l_ks,
+                                           u32 n) {
+    if constexpr (C::REP) flush_new<S, K, true>(P, B, lo, l_rel, l_lane, n);
+    else if constexpr (C::POOL) flush_pool<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
+    else if constexpr (C::DIST) flush_dist<S, K>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
+    else flush_new<S, K>(P, B, lo, l_rel, l_lane, n);
+}
+
+template <int S, int K, class C>
 __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi) {
+    constexpr bool SYM = C::SYM, DIST = C::DIST, VERIFY = C::VERIFY, PRE = C::PRE, SORT = C::SORT, DIA = C::DIA,
+                   REP = C::REP, PRESORT = C::PRESORT, POOL = C::POOL;
+    constexpr int BATCH = C::BATCH, WTILES = C::WTILES, PIPE = C::PIPE, DYN = C::DYN;
+    constexpr bool MARK = POOL || REP;  // send markers in the local set
     static_assert(!MARK || (DIST && !VERIFY && !SYM), "send markers: the plain sharded kernel only");
-    static_assert(!POOL || (MARK && !REP), "the pool flush: the send-marker kernel");
+    static_assert(!POOL || !REP, "the pool flush: not on a replicated level");
     constexpr bool SENTC = DIST && !MARK;  // the lossy sent-cache + (key, dest) list entries
-    static_assert(!DIA || (!SYM && !VERIFY), "diamond skipping: not under SYMMETRY or verification");
+    static_assert(!SENTC || !PRE, "the sent-cache kernels: every lane, no parent mixes");
+    static_assert(!DIA || (!SYM && !VERIFY && SORT), "diamond skipping: the sorted plain kernels");
     static_assert(!SORT || !VERIFY, "SORT: not with verification");
     static_assert(!SORT || BATCH * 7 <= 64, "SORT packs a batch's lanes 7 bits each into one u64");
     static_assert(PIPE == 0 || (!SYM && !VERIFY && !SENTC), "PIPE: the plain and marker kernels");
-    static_assert(!REP || (MARK && SORT && PRE), "replicated levels: the plain sharded kernel");
+    static_assert(!REP || (SORT && PRE), "replicated levels: the plain sharded kernel");
     // PRESORT: the windows were counting-sorted by class before the launch
     // (k_window_order writes each window's positions in class order to B.word),
     // so the kernel carries no sort: no LDS bins, scan or block barriers
@@ -1059,7 +1012,7 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
                     const int en = d.en && live;
                     g += (u32)(en && mine);
                     Fp h{0, 0};
-                    u64 hwn = 0;  // DIST: the mix of the changed server word (owner routing)
+                    u64 hwn = 0;  // REP: the mix of the changed server word (owner routing)
                     int in_model = 0;
                     if constexpr (SYM) {
                         // a stutter (successor = parent: no bag change, no word change) is never probed
@@ -1077,12 +1030,10 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
                         int nmb = 0;
                         if constexpr (PRE)
                             in_model = delta_fp_pre<S, K>(w, m, pmx, d, P, &h, DIA ? &nmb : nullptr,
-                                                          (REP || SENTC) ? &hwn : nullptr);
+                                                          REP ? &hwn : nullptr);
                         else in_model = delta_fp<S, K>(w, m, h0, d, P, &h, DIA ? &nmb : nullptr);
                         if constexpr (DIA)
-                            if (in_model && h.k != h0.k &&
-                                (SORT ? diamond_skip_desc<S, K>(m, lane, P.ldesc[SORT ? lane : 0], d, nmb, dm)
-                                      : diamond_skip<S, K>(m, lane, d, nmb, dm, P)))
+                            if (in_model && h.k != h0.k && diamond_skip_desc<S, K>(m, lane, P.ldesc[lane], d, nmb, dm))
                                 in_model = 0;
                     }
                     if (in_model && (SYM || h.k != h0.k)) {  // (a stutter has the parent's k)
@@ -1093,13 +1044,11 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
                         if constexpr (REP) {  // a replicated level: only the owner probes
                             if (owner_succ<S, K>(h.k, d, pmx, hwn, B, powner) != B.rank) key = 0;
                         } else if constexpr (SENTC) {
-                            if constexpr (PRE)
-                                s_own[b][threadIdx.x] = (uint8_t)owner_succ<S, K>(h.k, d, pmx, hwn, B, B.rank);
-                            else  // no parent mixes: the successor's words 0 and 1 when it changes one
-                                s_own[b][threadIdx.x] = (uint8_t)(
-                                    B.world == 1 ? 0u
-                                    : B.owner_mode == 0 ? owner_of(h.k, B.world)
-                                    : owner_succ_w<S>(h.k, d, w, B));
+                            // no parent mixes: the successor's hashed words when it changes one
+                            s_own[b][threadIdx.x] = (uint8_t)(
+                                B.world == 1 ? 0u
+                                : B.owner_mode == 0 ? owner_of(h.k, B.world)
+                                : owner_succ_w<S>(h.k, d, w, B));
                         }
                     }
                 }
@@ -1258,11 +1207,7 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
                     }
                     n += (u32)__popcll(bal);
                     if (n > (u32)(LCAP - 64)) {
-                        if constexpr (REP) flush_new<S, K, true>(P, B, lo, l_rel, l_lane, n);
-                        else if constexpr (POOL) flush_pool<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
-                        else if constexpr (MARK) flush_mark<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
-                        else if constexpr (DIST) flush_dist<S, K>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
-                        else flush_new<S, K>(P, B, lo, l_rel, l_lane, n);
+                        flush_list<S, K, C>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
                         n = 0;
                     }
                 }
@@ -1275,13 +1220,7 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
         gen += g;
     }
     }
-    if (n) {
-        if constexpr (REP) flush_new<S, K, true>(P, B, lo, l_rel, l_lane, n);
-        else if constexpr (POOL) flush_pool<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
-        else if constexpr (MARK) flush_mark<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
-        else if constexpr (DIST) flush_dist<S, K>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
-        else flush_new<S, K>(P, B, lo, l_rel, l_lane, n);
-    }
+    if (n) flush_list<S, K, C>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
     // wave reductions of the generated and probe counts, one atomic each per wave
     u64 gs = (u64)gen;
 #pragma unroll
@@ -1322,70 +1261,71 @@ __global__ __launch_bounds__(256) void k_capacity_check(const Params P, const De
     if (bad) atomicOr(&B.ctr->overflow, bad << 8);
 }
 
-// Every lane of every state (shapes with more than 64 lanes; verification).
-template <int S, int K, bool SYM, int BATCH, bool DIST, bool VERIFY = false, bool PRE = false>
+// Every lane of every state: full-state verification (single GPU and sharded)
+// and the sharded SYMMETRY search (the lossy sent-cache).
+template <bool SYM_, int BATCH_, bool DIST_, bool VERIFY_>
+struct ExpandEveryLane : ExpandDefaults {
+    static constexpr bool SYM = SYM_, DIST = DIST_, VERIFY = VERIFY_;
+    static constexpr int BATCH = BATCH_;
+};
+template <int S, int K, bool SYM, int BATCH, bool DIST, bool VERIFY = false>
 __global__ __launch_bounds__(256) void k_expand(const Params P, const PermTable PT, const DevBufs B, u64 lo, u64 hi) {
-    expand_body<S, K, SYM, BATCH, DIST, VERIFY, PRE>(P, PT, B, lo, hi);
+    static_assert(DIST || VERIFY, "the single-GPU searches have their own kernels (k_expand_sort, k_expand_sym)");
+    expand_body<S, K, ExpandEveryLane<SYM, BATCH, DIST, VERIFY>>(P, PT, B, lo, hi);
 }
 
 // The single-GPU expansion kernel: the lane-superset walk over windows of 16
-// tiles presorted by class (PS), commuting-diamond skipping, WPE waves/SIMD, DYN
-// dynamic per-wave work units; PI: probe loads issued during the lane code (K = 8
-// shapes would spill 10-13 VGPRs).
-template <int S, int K, int BATCH, int PI, bool PS = false, int WPE = 4, bool PRE = true, int DYN = 0>
+// tiles presorted by class (k_window_order), commuting-diamond skipping, the
+// parent's mixes recomputed per lane, dynamic per-wave work units, WPE
+// waves/SIMD; PI: probe loads issued during the lane code (K = 8 shapes would
+// spill 10-13 VGPRs).
+template <int BATCH_, int PI>
+struct ExpandSort : ExpandDefaults {
+    static constexpr bool SORT = true, PRESORT = true, DIA = true;
+    static constexpr int BATCH = BATCH_, WTILES = 16, PIPE = PI, DYN = 1;
+};
+template <int S, int K, int BATCH, int PI, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_expand_sort(
     const Params P, const PermTable PT, const DevBufs B, u64 lo, u64 hi) {
-    if constexpr (Lanes<S, K>::N <= 128)
-        expand_body<S, K, false, BATCH, false, false, PRE, true, true, false, 16, PI, false, PS, DYN>(P, PT, B, lo,
-                                                                                                     hi);
+    expand_body<S, K, ExpandSort<BATCH, PI>>(P, PT, B, lo, hi);
 }
 
 // SYMMETRY expansion: each lane fingerprints its successor under the
 // permutation that sorts the servers by signature, all S! only on ties
-// (deferred to k_ties).  WS: the lane-superset walk over class-sorted windows
-// of 16 tiles, 4 waves/SIMD (72.1-72.7 vs 75.0-75.3 ms for 8 tiles on the
-// MCraftBench bounds); otherwise (more than 64 lanes) every lane, 5 waves/SIMD.
-// (Round 4: windows presorted by k_window_order, 6 probes, 5 waves/SIMD measured
-// 78.0-78.5 vs 78.6-78.9 ms on the MCraftBench bounds, profiles/r04/ab/sym_variant_r04n.txt:
-// neutral, removed.)
-// PS (round 6, the default): the windows presorted by k_window_order, so the
-// block carries no LDS sort (35 instead of 48 KB: the 96-bit keys' s_ks array
-// had cut the in-kernel sort's block to 3 per CU, i.e. 3 waves/SIMD); with 6
-// probes in flight (BATCH) the block takes 28.7 KB and the kernel runs at 5 waves.
-template <int S, int K, int BATCH, bool WS, bool PS = false, int DYN = 0,
-          int WPE = (S == 3 && K == 4 ? (WS ? 4 : 5) : 1)>
+// (deferred to k_ties).  The lane-superset walk over windows of 16 tiles
+// presorted by k_window_order, so the block carries no LDS sort (35 instead of
+// 48 KB: the 96-bit keys' s_ks array had cut the in-kernel sort's block to 3
+// per CU, i.e. 3 waves/SIMD); with 6 probes in flight (BATCH) the block takes
+// 28.7 KB and the kernel runs at 5 waves (the shapes that fit 96 VGPRs).
+template <int BATCH_>
+struct ExpandSym : ExpandDefaults {
+    static constexpr bool SYM = true, SORT = true, PRESORT = true;
+    static constexpr int BATCH = BATCH_, WTILES = 16;
+};
+template <int S, int K, int BATCH, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 k_expand_sym(const Params P, const PermTable PT, const DevBufs B, u64 lo, u64 hi) {
-    if constexpr (WS && PS && Lanes<S, K>::N <= 128)
-        expand_body<S, K, true, BATCH, false, false, false, true, false, false, 16, 0, false, true, DYN>(P, PT, B, lo,
-                                                                                                       hi);
-    else if constexpr (WS && Lanes<S, K>::N <= 128)
-        expand_body<S, K, true, BATCH, false, false, false, true, false, false, 16>(P, PT, B, lo, hi);
-    else
-        expand_body<S, K, true, BATCH, false, false, false>(P, PT, B, lo, hi);
+    expand_body<S, K, ExpandSym<BATCH>>(P, PT, B, lo, hi);
 }
 
-
-
 // The sharded expansion: send markers in the local set, diamond skipping and
-// the lane-superset walk over class-sorted windows of 8 tiles (4 waves/SIMD;
-// uncapped it takes 131 VGPRs: 3 waves); every lane for more than 64 lanes.
-// REP: a replicated level (the whole level's records in B.rep).
-// POOL: the pool flush (flush_pool) with the single-GPU kernel's shape (presorted
-// windows of 16 tiles, early probe loads, the parent's mixes recomputed per lane).
-template <int S, int K, int BATCH, bool REP, bool PS = false, int WPE = 4, bool POOL = false, int DYN = 0>
+// the lane-superset walk, in two forms.
+// The pool flush (flush_pool) at the single-GPU kernel's shape: presorted
+// windows of 16 tiles, early probe loads (K <= 4), the parent's mixes
+// recomputed per lane.
+// REP: a replicated level (the whole level's records in B.rep): windows of 8
+// tiles sorted in LDS by the kernel, the parent's mixes held (the owner of
+// every probe is computed from them), 4 waves/SIMD.
+template <int K, int BATCH_, bool REP_>
+struct ExpandDist : ExpandDefaults {
+    static constexpr bool DIST = true, SORT = true, DIA = true;
+    static constexpr bool REP = REP_, POOL = !REP_, PRE = REP_, PRESORT = !REP_;
+    static constexpr int BATCH = BATCH_, WTILES = REP_ ? 8 : 16, PIPE = !REP_ && K <= 4 ? 1 : 0;
+};
+template <int S, int K, int BATCH, bool REP, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_expand_dist(
     const Params P, const PermTable PT, const DevBufs B, u64 lo, u64 hi) {
-    if constexpr (Lanes<S, K>::N <= 128 && POOL && !REP)
-        expand_body<S, K, false, BATCH, true, false, false, true, true, true, 16, K <= 4 ? 1 : 0, false, true, DYN,
-                    true>(P, PT, B, lo, hi);
-    else if constexpr (POOL && !REP)  // more than 64 lanes: every lane, the pool flush
-        expand_body<S, K, false, BATCH, true, false, false, false, false, true, 8, 0, false, false, 0, true>(P, PT, B,
-                                                                                                           lo, hi);
-    else if constexpr (Lanes<S, K>::N <= 128)
-        expand_body<S, K, false, BATCH, true, false, true, true, true, true, 8, 0, REP>(P, PT, B, lo, hi);
-    else if constexpr (!REP)
-        expand_body<S, K, false, BATCH, true, false, false, false, false, true>(P, PT, B, lo, hi);
+    expand_body<S, K, ExpandDist<K, BATCH, REP>>(P, PT, B, lo, hi);
 }
 
 #ifndef RMC_SHAPE_S  // non-template kernels: in the common object only
@@ -1636,12 +1576,9 @@ __global__ __launch_bounds__(256) void k_route_fix(const Params P, const DevBufs
         const u64 tk = B.ovf[3 * q + 2];
         const u64 pidx = tk & ((1ull << 48) - 1);
         const int lane = (int)(tk >> 56);
-        u64 w[S], wo[S];
-        u32 m[K], mo[K];
-        load_state<S, K>(B.store + pidx * (u64)NW, w, m);
-        Delta d;
-        lane_delta<S, K>(w, m, lane, P, d);
-        materialise<S, K>(w, m, d, wo, mo);
+        u64 wo[S];
+        u32 mo[K];
+        derive_succ<S, K>(B.store + pidx * (u64)NW, lane, P, wo, mo);
         const Fp key = fp_of_materialised<S, K>(wo, mo, P);
         B.ovf[3 * q] = key.k;
         B.ovf[3 * q + 2] = pidx | ((u64)owner_state<S>(key.k, wo, B) << 48) | ((u64)lane << 56);
@@ -1707,20 +1644,12 @@ __global__ __launch_bounds__(256) void k_materialize_remote(const Params P, cons
 template <int S, int K>
 __global__ __launch_bounds__(256) void k_store_remote(const Params P, const DevBufs B, const u32* inbox, u64 n) {
     constexpr int NW = 2 * S + K, RW = NW + 4;  // state, parent ref, footprint
-    const int me = (int)__lane_id();
-    const u64 lt = (1ull << me) - 1ull;
     for (u64 t0 = (u64)blockIdx.x * 256ull; t0 < n; t0 += (u64)gridDim.x * 256ull) {
         const u64 t = t0 + threadIdx.x;
         // verification mode also receives the states the owner had seen (compared by k_compare_remote)
         const bool live = t < n && !(inbox[t * (u64)RW + NW + 1] & (u32)(REF_SEEN >> 32));
-        const u64 bal = __ballot(live);
-        if (!bal) continue;
-        const int leader = __ffsll((long long)bal) - 1;
-        u64 base = 0;
-        if (me == leader) base = atomicAdd((unsigned long long*)&B.ctr->count, (unsigned long long)__popcll(bal));
-        base = bcast64(base, leader);
+        const u64 ni = wave_reserve(live, (unsigned long long*)&B.ctr->count);
         if (!live) continue;
-        const u64 ni = base + (u64)__popcll(bal & lt);
         if (ni >= B.cap) {
             atomicOr(&B.ctr->overflow, 1u);
             continue;
@@ -2134,191 +2063,127 @@ static u64 resident_grid(const void* k) {
     return v;
 }
 
-// Expansion kernel variant (RMC_EXPAND_VARIANT): 20 (the default, any value but 1)
-// = k_expand_sort over windows of 16 tiles presorted by class (k_window_order; no
-// sort in the kernel, so a smaller block), 5 probes in flight per thread, the
-// parent's mixes recomputed per lane (80 VGPRs: 6 waves/SIMD; 5 waves for S >= 4), each wave taking its
-// next quarter-window from a launch-wide counter (XL 739.3-741.6 vs 760.1-762.1 ms
-// for fixed per-block shares, profiles/r05/variants/); 1 = every lane of every
-// state (k_expand, the kernel of shapes with more than 128 lanes).  The variants
-// measured and rejected in rounds 2-5 (6 probes at 5 waves with the mixes held,
-// windows sorted in LDS, fixed shares, 4-8 probes at 4-6 waves, prefetching, 64-B
-// store records) are in git history; their numbers are in DESIGN.md §Kernels.
-static int expand_variant() {
-    static int v = [] {
-        const char* e = getenv("RMC_EXPAND_VARIANT");
-        return e ? atoi(e) : 20;
-    }();
-    return v;
-}
-
-// Sharded expansion kernel (RMC_DIST_KVARIANT): 3 (the default, any value but 0)
-// = the pool flush at the single-GPU kernel's shape (presorted windows, 5 probes,
-// 6 waves/SIMD; remote successors pooled whole and routed by k_route after the
-// launch); 0 = the round-3 send-marker kernel with the flush doing the routing
-// (windows sorted in LDS).  The other variants measured in rounds 3-6
-// (profiles/r04/ab/dist_kvariant_*, profiles/r05/kv4/; dynamic per-wave units a
-// tie again in round 6, profiles/r06/ab/dist_kvariant_3_4.txt) are in git history.
-static int dist_kvariant() {
-    static int v = [] {
-        const char* e = getenv("RMC_DIST_KVARIANT");
-        return e ? atoi(e) : 3;
-    }();
-    return v;
-}
-
-// SYMMETRY expansion kernel (RMC_SYM_VARIANT): 2 (default) windows presorted by
-// k_window_order, 6 probes in flight, 5 waves/SIMD (96 VGPRs, 28.7 KB of LDS:
-// 79-80 ms on MCraftBenchSym, profiles/r06/ab/sym_batch6_5waves.txt); 1 the same
-// with 8 probes at 4 waves (81-82 ms; dynamic per-wave units and other grids
-// measured the same, profiles/r06/ab/sym_presorted.txt); 0 windows sorted in LDS
-// by the kernel itself (round 5: 48 KB of LDS, 3 waves/SIMD, 87-88 ms).
-static int sym_variant() {
-    static int v = [] {
-        const char* e = getenv("RMC_SYM_VARIANT");
-        return e ? atoi(e) : 2;
-    }();
-    return v;
-}
-
-// Probes in flight per thread: 8 (measured best of 4/8/16 on MI355X).
+// Probes in flight per thread of the every-lane kernels: 8 (measured best of
+// 4/8/16 on MI355X).  The presorted plain kernels keep 5 (80 VGPRs: 6
+// waves/SIMD), the SYMMETRY kernel 6 where it then fits 5 waves.  The variants
+// measured and rejected in rounds 2-6 (the mixes held, windows sorted in LDS,
+// fixed shares, 4-8 probes at 4-6 waves, prefetching, 64-B store records, the
+// flush doing the routing) are in git history; their numbers are in DESIGN.md
+// §Kernels.
 constexpr int kBatch = 8;
 
 template <int S, int K, bool SYM>
-static hipError_t launch_t(int which, bool verify, const Params& P, const PermTable& PT, const DevBufs& B, u64 a,
-                           u64 b, const u32* in, u32* out, u64 cap, unsigned long long* count, hipStream_t st) {
-    const u64 n = (which == 0 || which == 3 || which == 5 || which == 7 || which == 12 || which == 13) ? (b - a)
-                : which == 8 ? a * (u64)B.world : (which == 10 || which == 14) ? 1 : a;
+static hipError_t launch_t(Op op, bool verify, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
+                           const u32* in, u32* out, u64 cap, unsigned long long* count, hipStream_t st) {
+    // every kernel of this object walks lanes through the 128-bit LaneMask and
+    // the lane descriptors; a wider shape needs its own walk
+    static_assert(Lanes<S, K>::N <= 128, "a shape's lanes must fit the 128-bit lane mask");
+    u64 n = a;  // work items of the launch
+    switch (op) {
+    case Op::Expand: case Op::ExpandDist: case Op::ExpandRep: case Op::Publish: case Op::Rehash: case Op::PackRep:
+        n = b - a;
+        break;
+    case Op::MaterializeRemote: n = a * (u64)B.world; break;
+    case Op::Ties: case Op::Route: n = 1; break;  // their counts are on the device
+    default: break;
+    }
     if (n == 0) return hipSuccess;
     const u64 blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    // grid-stride kernels: 2048 blocks; the plain and sharded expansion kernels
-    // one round of resident blocks (resident_grid at their launch below;
-    // SYMMETRY keeps 2048: 79.7 vs 81.5 ms on the MCraftBench bounds)
-    const u64 grid = (u64)2048;
-    const u64 g = blocks < grid ? blocks : grid;
-    // the expansion kernels' grid: RMC_EXPAND_GRID, else one round of resident blocks
-    auto eg = [&](const void* k) -> unsigned {
-        const u64 want = expand_grid_env() ? expand_grid_env() : resident_grid(k);
-        return (unsigned)(blocks < want ? blocks : want);
+    // grid-stride kernels: 2048 blocks
+    const dim3 g((unsigned)(blocks < 2048 ? blocks : 2048)), tpb(256);
+    // One expansion launch: `kernel` on RMC_EXPAND_GRID blocks, else on `dflt`
+    // blocks (0: one round of the kernel's resident blocks); presorted: after
+    // k_window_order over the same launch and grid.
+    auto expand = [&](auto kernel, bool presorted, u64 dflt = 0) -> hipError_t {
+        const u64 want = expand_grid_env() ? expand_grid_env()
+                         : dflt            ? dflt
+                                           : resident_grid(reinterpret_cast<const void*>(kernel));
+        const u64 eg = blocks < want ? blocks : want;
+        if (presorted)
+            if (hipError_t e = launch_window_order(B, a, b, eg, 16, st)) return e;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)eg), tpb, 0, st, P, PT, B, a, b);
+        return hipSuccess;
     };
-#define RMC_EXPAND_LAUNCH(KERNEL)                                                                              \
-    hipLaunchKernelGGL(KERNEL, dim3(eg(reinterpret_cast<const void*>(&(KERNEL)))), dim3(256), 0, st, P, PT, B, a, b)
-    constexpr bool SORTED = Lanes<S, K>::N <= 128;  // every shape: the lane-superset walk (LaneMask)
-    if (which == 0) {
+    hipError_t e = hipSuccess;
+    switch (op) {
+    case Op::Expand:
         if constexpr (SYM) {
-            if (verify)
-                hipLaunchKernelGGL((k_expand<S, K, true, kBatch, false, true>), dim3((unsigned)g), dim3(256), 0, st, P,
-                                   PT, B, a, b);
-            else if (sym_variant() >= 2 && S <= 3 && K == 4 && SORTED && B.word) {
-                // presorted, 6 probes in flight, 5 waves/SIMD (the shapes that fit 96 VGPRs
-                // without spills; the others take variant 1)
-                if constexpr (S <= 3 && K == 4) {
-                    const u64 gs = expand_grid_env() ? (blocks < expand_grid_env() ? blocks : expand_grid_env()) : g;
-                    if (hipError_t e = launch_window_order(B, a, b, gs, 16, st)) return e;
-                    hipLaunchKernelGGL((k_expand_sym<S, K, 6, SORTED, true, 0, 5>), dim3((unsigned)gs), dim3(256), 0,
-                                       st, P, PT, B, a, b);
-                }
-            } else if (sym_variant() != 0 && SORTED && B.word) {  // windows presorted by k_window_order
-                const u64 gs = expand_grid_env() ? (blocks < expand_grid_env() ? blocks : expand_grid_env()) : g;
-                if (hipError_t e = launch_window_order(B, a, b, gs, 16, st)) return e;
-                hipLaunchKernelGGL((k_expand_sym<S, K, kBatch, SORTED, true>), dim3((unsigned)gs), dim3(256), 0, st, P,
-                                   PT, B, a, b);
-            } else
-                hipLaunchKernelGGL((k_expand_sym<S, K, kBatch, SORTED>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B,
-                                   a, b);
+            // SYMMETRY keeps 2048 blocks: 79.7 vs 81.5 ms on the MCraftBench bounds
+            if (verify) {
+                hipLaunchKernelGGL((k_expand<S, K, true, kBatch, false, true>), g, tpb, 0, st, P, PT, B, a, b);
+            } else if constexpr (S <= 3 && K == 4) {
+                // 6 probes in flight, 5 waves/SIMD: the shapes that fit 96 VGPRs without spills
+                e = expand(&k_expand_sym<S, K, 6, 5>, true, 2048);
+            } else {
+                e = expand(&k_expand_sym<S, K, kBatch, 1>, true, 2048);
+            }
         } else if (verify) {
-            RMC_EXPAND_LAUNCH((k_expand<S, K, false, kBatch, false, true>));
-        } else if (expand_variant() != 1 && S >= 4 && SORTED && B.word) {
-            // S >= 4 (68 / 92 lanes, the 128-bit lane mask): the same kernel at 5 waves/SIMD
-            // (96 VGPRs, 16 B of scratch) beats 6 waves with 48 B of spills: MCraft5 -depth 20
-            // 206 vs 245-246 ms (4 probes at 6 waves 247-248 ms), profiles/r06/ab/s5_waves.txt
-            if constexpr (S >= 4) {
-                const void* kp = reinterpret_cast<const void*>(&(k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, true, 5, false, 1>));
-                const u64 want = expand_grid_env() ? expand_grid_env() : resident_grid(kp);
-                if (hipError_t e = launch_window_order(B, a, b, want, 16, st)) return e;
-                RMC_EXPAND_LAUNCH((k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, true, 5, false, 1>));
-            }
-        } else if (expand_variant() != 1 && S < 4 && SORTED && B.word) {  // 20: presorted windows, dynamic units
-            if constexpr (S < 4) {
-                const void* kp = reinterpret_cast<const void*>(&(k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, true, 6, false, 1>));
-                const u64 want = expand_grid_env() ? expand_grid_env() : resident_grid(kp);
-                if (hipError_t e = launch_window_order(B, a, b, want, 16, st)) return e;
-                RMC_EXPAND_LAUNCH((k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, true, 6, false, 1>));
-            }
-        } else {  // 1, and shapes with more than 64 lanes
-            RMC_EXPAND_LAUNCH((k_expand<S, K, false, kBatch, false, false, true>));
+            e = expand(&k_expand<S, K, false, kBatch, false, true>, false);
+        } else {
+            // 5 probes, 6 waves/SIMD (80 VGPRs).  S >= 4 (68 / 92 lanes): 5 waves (96 VGPRs,
+            // 16 B of scratch) beat 6 waves with 48 B of spills: MCraft5 -depth 20 206 vs
+            // 245-246 ms (4 probes at 6 waves 247-248 ms), profiles/r06/ab/s5_waves.txt
+            e = expand(&k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, S >= 4 ? 5 : 6>, true);
         }
-    } else if (which == 3 && verify) {  // sharded full-state verification: every lane, hits compared
-        RMC_EXPAND_LAUNCH((k_expand<S, K, SYM, kBatch, true, true>));
-    } else if (which == 3) {
-        if constexpr (SYM) RMC_EXPAND_LAUNCH((k_expand<S, K, SYM, kBatch, true>));  // the lossy sent-cache
-        else if (dist_kvariant() != 0 && S >= 4 && B.pool) {
-            // S >= 4: 5 waves/SIMD (96 VGPRs) instead of 6 with 96 B of spills: MCraft5 to
-            // depth 20 on one sharded rank 0.322 vs 0.568 s (profiles/r06/ab/s5_dist_waves.txt)
-            if constexpr (SORTED && S >= 4) {
-                const void* kp = reinterpret_cast<const void*>(&(k_expand_dist<S, K, 5, false, true, 5, true>));
-                const u64 want = expand_grid_env() ? expand_grid_env() : resident_grid(kp);
-                if (hipError_t e = launch_window_order(B, a, b, want, 16, st)) return e;
-                RMC_EXPAND_LAUNCH((k_expand_dist<S, K, 5, false, true, 5, true>));
-            }
-        } else if (dist_kvariant() != 0 && B.pool) {  // 3: the pool flush at the single-GPU kernel's shape
-            if constexpr (SORTED && S < 4) {
-                const void* kp = reinterpret_cast<const void*>(&(k_expand_dist<S, K, 5, false, true, 6, true>));
-                const u64 want = expand_grid_env() ? expand_grid_env() : resident_grid(kp);
-                if (hipError_t e = launch_window_order(B, a, b, want, 16, st)) return e;
-                RMC_EXPAND_LAUNCH((k_expand_dist<S, K, 5, false, true, 6, true>));
-            } else if constexpr (!SORTED) {
-                RMC_EXPAND_LAUNCH((k_expand_dist<S, K, kBatch, false, false, 4, true>));
-            }
-        } else RMC_EXPAND_LAUNCH((k_expand_dist<S, K, kBatch, false>));            // send markers
-    } else if (which == 12) {  // a replicated level: records [a, b) of B.rep (plain kernel, <= 64 lanes)
-        if constexpr (!SYM && SORTED) RMC_EXPAND_LAUNCH((k_expand_dist<S, K, kBatch, true>));
+        break;
+    case Op::ExpandDist:
+        if (verify) {  // sharded full-state verification: every lane, hits compared
+            e = expand(&k_expand<S, K, SYM, kBatch, true, true>, false);
+        } else if constexpr (SYM) {  // the lossy sent-cache
+            e = expand(&k_expand<S, K, true, kBatch, true>, false);
+        } else {
+            // the pool flush at the single-GPU kernel's shape.  S >= 4: 5 waves/SIMD (96
+            // VGPRs) instead of 6 with 96 B of spills: MCraft5 to depth 20 on one sharded
+            // rank 0.322 vs 0.568 s (profiles/r06/ab/s5_dist_waves.txt)
+            e = expand(&k_expand_dist<S, K, 5, false, S >= 4 ? 5 : 6>, true);
+        }
+        break;
+    case Op::ExpandRep:  // a replicated level: records [a, b) of B.rep (the plain search only)
+        if constexpr (!SYM) e = expand(&k_expand_dist<S, K, kBatch, true, 4>, false);
         else return hipErrorInvalidValue;
-    } else if (which == 14) {  // the pool's records to the outboxes (after a pool-flush expansion)
+        break;
+    case Op::Route:  // the pool's records to the outboxes (after a pool-flush expansion)
         if constexpr (!SYM) {
-            hipLaunchKernelGGL((k_route_fix<S, K>), dim3(256), dim3(256), 0, st, P, B);
-            hipLaunchKernelGGL((k_route<S, K>), dim3(1024), dim3(256), 0, st, P, B);
+            hipLaunchKernelGGL((k_route_fix<S, K>), dim3(256), tpb, 0, st, P, B);
+            hipLaunchKernelGGL((k_route<S, K>), dim3(1024), tpb, 0, st, P, B);
         } else {
             return hipErrorInvalidValue;
         }
-    } else if (which == 13) {
-        hipLaunchKernelGGL((k_pack_rep<S, K>), dim3((unsigned)g), dim3(256), 0, st, B, a, b, out);
-    } else if (which == 11) {
-        hipLaunchKernelGGL((k_compare_remote<S, K, SYM>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B, in, a);
-    } else if (which == 8) {  // a = keys per destination block (max); out = replies
-        hipLaunchKernelGGL((k_materialize_remote<S, K>), dim3((unsigned)g), dim3(256), 0, st, P, B,
-                           reinterpret_cast<const uint8_t*>(in), a, b);
-    } else if (which == 9) {
-        hipLaunchKernelGGL((k_store_remote<S, K>), dim3((unsigned)g), dim3(256), 0, st, P, B, in, a);
-    } else if (which == 10) {
-        if constexpr (SYM) hipLaunchKernelGGL((k_ties<S, K>), dim3(1024), dim3(256), 0, st, P, PT, B);
-    } else if (which == 5) {
-        hipLaunchKernelGGL((k_publish<S, K, SYM>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B, a, b);
-    } else if (which == 7) {
-        hipLaunchKernelGGL((k_rehash<S, K, SYM>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B, a, b);
-    } else if (which == 6) {
-        hipLaunchKernelGGL((k_verify<S, K, SYM>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B, a);
-    } else if (which == 15) {
-        hipLaunchKernelGGL((k_verify_host<S, K, SYM>), dim3((unsigned)g), dim3(256), 0, st, P, PT, B, in, a, b);
-    } else if (which == 1) {
-        hipLaunchKernelGGL((k_seed<S, K, SYM>), dim3((unsigned)blocks), dim3(256), 0, st, P, PT, B, in, a);
-    } else {
-        hipLaunchKernelGGL((k_list<S, K, SYM>), dim3((unsigned)blocks), dim3(256), 0, st, P, PT, in, a, out, cap,
-                           count);
+        break;
+    case Op::PackRep: hipLaunchKernelGGL((k_pack_rep<S, K>), g, tpb, 0, st, B, a, b, out); break;
+    case Op::CompareRemote: hipLaunchKernelGGL((k_compare_remote<S, K, SYM>), g, tpb, 0, st, P, PT, B, in, a); break;
+    case Op::MaterializeRemote:  // a = keys per destination block (max); in = replies
+        hipLaunchKernelGGL((k_materialize_remote<S, K>), g, tpb, 0, st, P, B, reinterpret_cast<const uint8_t*>(in), a,
+                           b);
+        break;
+    case Op::StoreRemote: hipLaunchKernelGGL((k_store_remote<S, K>), g, tpb, 0, st, P, B, in, a); break;
+    case Op::Ties:
+        if constexpr (SYM) hipLaunchKernelGGL((k_ties<S, K>), dim3(1024), tpb, 0, st, P, PT, B);
+        break;
+    case Op::Publish: hipLaunchKernelGGL((k_publish<S, K, SYM>), g, tpb, 0, st, P, PT, B, a, b); break;
+    case Op::Rehash: hipLaunchKernelGGL((k_rehash<S, K, SYM>), g, tpb, 0, st, P, PT, B, a, b); break;
+    case Op::Verify: hipLaunchKernelGGL((k_verify<S, K, SYM>), g, tpb, 0, st, P, PT, B, a); break;
+    case Op::VerifyHost: hipLaunchKernelGGL((k_verify_host<S, K, SYM>), g, tpb, 0, st, P, PT, B, in, a, b); break;
+    case Op::Seed:
+        hipLaunchKernelGGL((k_seed<S, K, SYM>), dim3((unsigned)blocks), tpb, 0, st, P, PT, B, in, a);
+        break;
+    case Op::List:
+        hipLaunchKernelGGL((k_list<S, K, SYM>), dim3((unsigned)blocks), tpb, 0, st, P, PT, in, a, out, cap, count);
+        break;
     }
-#undef RMC_EXPAND_LAUNCH
-    if ((which == 0 || which == 3) && P.unbounded)  // depth-bounded unconstrained model: the capacity pass
-        hipLaunchKernelGGL((k_capacity_check<S, K>), dim3((unsigned)g), dim3(256), 0, st, P, B, a, b);
+    if (e != hipSuccess) return e;
+    if ((op == Op::Expand || op == Op::ExpandDist) && P.unbounded)  // depth-bounded unconstrained model: the capacity pass
+        hipLaunchKernelGGL((k_capacity_check<S, K>), g, tpb, 0, st, P, B, a, b);
     return hipGetLastError();
 }
 
 template <int S, int K>
-static hipError_t launch_sk(bool sym, bool verify, int which, const Params& P, const PermTable& PT, const DevBufs& B,
+static hipError_t launch_sk(bool sym, bool verify, Op op, const Params& P, const PermTable& PT, const DevBufs& B,
                             u64 a, u64 b, const u32* in, u32* out, u64 cap, unsigned long long* count,
                             hipStream_t st) {
-    if (sym) return launch_t<S, K, true>(which, verify, P, PT, B, a, b, in, out, cap, count, st);
-    return launch_t<S, K, false>(which, verify, P, PT, B, a, b, in, out, cap, count, st);
+    if (sym) return launch_t<S, K, true>(op, verify, P, PT, B, a, b, in, out, cap, count, st);
+    return launch_t<S, K, false>(op, verify, P, PT, B, a, b, in, out, cap, count, st);
 }
 
 // ---- objects: one per shape (RMC_SHAPE_S / RMC_SHAPE_K, the template
@@ -2326,7 +2191,7 @@ static hipError_t launch_sk(bool sym, bool verify, int which, const Params& P, c
 // shape-free kernels).  The fingerprint salt is a __constant__ of each object.
 #define RMC_SHAPES(X) X(2, 4) X(2, 8) X(3, 4) X(3, 8) X(4, 4) X(4, 8) X(5, 4) X(5, 8)
 #define RMC_SHAPE_DECLS(SS, KK)                                                                                 \
-    hipError_t launch_shape_##SS##_##KK(const Shape& sh, int which, const Params& P, const PermTable& PT,       \
+    hipError_t launch_shape_##SS##_##KK(const Shape& sh, Op op, const Params& P, const PermTable& PT,           \
                                         const DevBufs& B, u64 a, u64 b, const u32* in, u32* out, u64 cap,       \
                                         unsigned long long* count, hipStream_t st);                             \
     hipError_t launch_sim_shape_##SS##_##KK(const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, \
@@ -2337,10 +2202,10 @@ RMC_SHAPES(RMC_SHAPE_DECLS)
 
 #ifdef RMC_SHAPE_S
 #define RMC_DEFINE_SHAPE(SS, KK)                                                                                \
-    hipError_t launch_shape_##SS##_##KK(const Shape& sh, int which, const Params& P, const PermTable& PT,       \
+    hipError_t launch_shape_##SS##_##KK(const Shape& sh, Op op, const Params& P, const PermTable& PT,           \
                                         const DevBufs& B, u64 a, u64 b, const u32* in, u32* out, u64 cap,       \
                                         unsigned long long* count, hipStream_t st) {                            \
-        return launch_sk<SS, KK>(sh.sym, sh.verify, which, P, PT, B, a, b, in, out, cap, count, st);           \
+        return launch_sk<SS, KK>(sh.sym, sh.verify, op, P, PT, B, a, b, in, out, cap, count, st);              \
     }                                                                                                           \
     hipError_t launch_sim_shape_##SS##_##KK(const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, \
                                             u64 seed, int mode, SimCounters* out, i64 rec_beh, u32* rec,        \
@@ -2380,10 +2245,10 @@ hipError_t set_fp_salt(const Shape& sh, u64 seed, u32 set_epoch, hipStream_t st)
     return hipErrorInvalidValue;
 }
 
-hipError_t launch(const Shape& sh, int which, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
+hipError_t launch(const Shape& sh, Op op, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
                   const u32* in, u32* out, u64 cap, unsigned long long* count, hipStream_t st) {
 #define RMC_CASE(SS, KK) \
-    if (sh.S == SS && sh.K == KK) return launch_shape_##SS##_##KK(sh, which, P, PT, B, a, b, in, out, cap, count, st);
+    if (sh.S == SS && sh.K == KK) return launch_shape_##SS##_##KK(sh, op, P, PT, B, a, b, in, out, cap, count, st);
     RMC_SHAPES(RMC_CASE)
 #undef RMC_CASE
     return hipErrorInvalidValue;

@@ -168,6 +168,9 @@ struct Model {
                         if (dd.en != d.en || dd.srv != d.srv || dd.rm != d.rm || dd.has_add != d.has_add ||
                             (d.en && (dd.w_new != d.w_new || dd.add != d.add)))
                             ++o.mismatch;
+                        // ... and the same footprint word (the flushes of the sorted kernels)
+                        if (d.en && make_foot_desc<S, K>(m, P.ldesc[lane], dd) != make_foot<S, K>(m, lane, d, P))
+                            ++o.mismatch;
                     }
                     if (!d.en) continue;
                     ++o.generated;

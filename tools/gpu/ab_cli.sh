@@ -1,6 +1,6 @@
 # Same-box A/B of a knob on an rmc-tlc run (its "Finished in" line), after
 # the knob's GPU parity tests:
-#   KNOB=RMC_SYM_VARIANT VARS="0 1" ARGS="-builtin-raft specs/MCraftBenchSym.tla"
+#   KNOB=RMC_EXPAND_GRID VARS="1024 2048" ARGS="-builtin-raft specs/MCraftBenchSym.tla"
 #   [PARITY="tests/test_gpu.py -k sym"] [ROUNDS=3] [OUT=gpurun_out/abc] bash tools/gpu/ab_cli.sh
 # Each round runs every value once, the order rotated by one per round.
 set -o pipefail

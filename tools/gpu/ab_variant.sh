@@ -1,6 +1,6 @@
 # Same-box A/B of a kernel knob on the bench model, after parity of each value
 # on the BFS fixtures:
-#   VARS="6 7" [KNOB=RMC_EXPAND_VARIANT] [PARITY="tests/test_gpu.py -k 'bfs_matches_oracle or salt'"]
+#   VARS="1024 2048" [KNOB=RMC_EXPAND_GRID] [PARITY="tests/test_gpu.py -k 'bfs_matches_oracle or salt'"]
 #   [BENCH_EXTRA="--force-dist"] [ROUNDS=2] [OUT=gpurun_out/ab] bash tools/gpu/ab_variant.sh
 # Each round runs every value once, the order rotated by one per round (a
 # value's place in the round does not favour it).
@@ -8,8 +8,8 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${OUT:-gpurun_out/ab}
 mkdir -p $O
-KNOB=${KNOB:-RMC_EXPAND_VARIANT}
-VARS=${VARS:-"6 7"}
+KNOB=${KNOB:-RMC_EXPAND_GRID}
+VARS=${VARS:-"1024 2048"}
 PARITY=${PARITY:-"tests/test_gpu.py -k 'bfs_matches_oracle or salt'"}
 for v in $VARS; do
   env $KNOB=$v timeout -k 10 400 bash -c "python -u -m pytest $PARITY -x -q --timeout 240 --timeout-method thread" > $O/parity_$v.log 2>&1 || { tail -20 $O/parity_$v.log; exit 1; }

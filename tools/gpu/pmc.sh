@@ -1,7 +1,7 @@
 # rocprofv3 evidence for the bench command (the build in the tree):
 # a kernel trace with stats, then one PMC pass per counter group (separate
 # runs: FETCH_SIZE and WRITE_SIZE alone, instruction mix, waits, LDS, atomics).
-#   OUT=gpurun_out/<tag> [ENVS="RMC_EXPAND_VARIANT=7"] [CMD="raft.tla_amd/bin/rmc-tlc ..."] bash tools/gpu/pmc.sh
+#   OUT=<output dir> [ENVS="RMC_DIAMOND=0"] [CMD="raft.tla_amd/bin/rmc-tlc ..."] bash tools/gpu/pmc.sh
 # (CMD replaces the bench command; it must be the program itself, no wrapper)
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -37,10 +37,11 @@ extern "C" {
 #define RMC_MAX_DUP 3      /* per-message count bound <= 3 */
 /* Capacity of the wide encoding (DESIGN.md "Wide state"): a model with any
  * bound beyond the packed capacity — or a field no CONSTRAINT bounds, under a
- * depth bound or in simulation — runs on it (single GPU; no SYMMETRY,
- * verification or spill).  A CONSTRAINT bound must stay below the wide
- * capacity; an unbounded field is given the capacity itself, and a successor
- * beyond it stops the search with RMC_E_CAPACITY naming the field. */
+ * depth bound or in simulation — runs on it (single GPU; no SYMMETRY or
+ * verification; RMC_FLAG_SPILL keeps its records in a ring window).  A
+ * CONSTRAINT bound must stay below the wide capacity; an unbounded field is
+ * given the capacity itself, and a successor beyond it stops the search with
+ * RMC_E_CAPACITY naming the field. */
 #define RMC_WIDE_MAX_TERM 255
 #define RMC_WIDE_MAX_LOG 32
 #define RMC_WIDE_MAX_MSGS 64
@@ -82,7 +83,13 @@ extern "C" {
                                            /* RMC_FLAG_VERIFY_STATES every state leaving */
                                            /* the window keeps a host copy, and hits on  */
                                            /* it are compared with that copy (round 6;   */
-                                           /* no checkpoint / recover then)             */
+                                           /* no checkpoint / recover then).  On the    */
+                                           /* wide layout: a ring of exactly             */
+                                           /* device_window records, the links always in */
+                                           /* HBM; a run bounded by max_depth does not   */
+                                           /* store its last level (never expanded), so  */
+                                           /* its record is sized one level shallower;   */
+                                           /* traces are replayed from Init              */
 /* A model without a CONSTRAINT on some field (MCraft.cfg as shipped) runs only
  * under a depth bound (max_depth > 0, TLC -depth).  The front-end then gives
  * each unbounded field the wide capacity (RMC_WIDE_MAX_TERM, RMC_WIDE_MAX_LOG,
@@ -292,7 +299,8 @@ int rmc_recover(rmc_ctx* ctx, const char* path);
 
 /* ---- codec and successor enumeration (tests, Java driver printing) -------
  * rmc_state_bytes: bytes of one stored state for this config (packed, or the
- * wide layout's BFS record: 904 B compact or 5,080 B).
+ * wide layout's BFS store record: 336 B depth-sized, 904 B compact or 5,080 B;
+ * with RMC_FLAG_SPILL and max_depth the record of the last stored level).
  * rmc_expand: run the SAME device successor code as the BFS on n caller
  * states (no dedup) and return every enabled lane's successor.  *n_out
  * receives the number of successors even if it exceeds cap. */

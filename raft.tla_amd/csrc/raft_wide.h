@@ -153,6 +153,68 @@ RMC_HD void wmsg_zero(Mg& m) {
     for (int k = 0; k < (int)(sizeof(Mg) / 8); ++k) x[k] = 0;
 }
 
+// The same state in another record type (the spilled BFS stores one type and
+// works on a larger one).  Every record type orders its bag alike: a message
+// is its 8-byte header word, then its entries four to a word, compared in turn
+// (wmsg_cmp), and the entries a shorter record lacks are 0 in the longer one, so
+// bag slot q is the same message in both — a bag lane names the same action on
+// either.  wnarrow_bits: the fields of t a Dst record cannot hold (the
+// Counters.overflow field bits of woverflow_bits: 2 a log or a RequestVoteResponse's
+// mlog, 4 the bag), 0 when wconvert loses nothing.  wconvert writes every byte of d.
+template <class Dst, class Src>
+RMC_HD int wnarrow_bits(const Src& t) {
+    int bits = 0;
+    if (Dst::kLW < Src::kLW) {
+        for (int i = 0; i < WS; ++i)
+            if (t.len[i] > Dst::kLW) bits |= 2;
+        for (int q = 0; q < t.nmsg; ++q)
+            if (t.msg[q].n > Dst::kLW) bits |= 2;  // (an AppendEntriesRequest carries at most 1 entry)
+    }
+    if (Dst::kKW < Src::kKW && t.nmsg > Dst::kKW) bits |= 4;
+    return bits;
+}
+template <class Dst, class Src>
+RMC_HD void wconvert(Dst& d, const Src& s) {
+    constexpr int L = Dst::kLW < Src::kLW ? Dst::kLW : Src::kLW, K = Dst::kKW < Src::kKW ? Dst::kKW : Src::kKW;
+    for (int i = 0; i < WS; ++i) {
+        d.ct[i] = s.ct[i];
+        d.st[i] = s.st[i];
+        d.vf[i] = s.vf[i];
+        d.ci[i] = s.ci[i];
+        d.len[i] = s.len[i];
+        d.vR[i] = s.vR[i];
+        d.vG[i] = s.vG[i];
+        for (int j = 0; j < WS; ++j) {
+            d.ni[i][j] = s.ni[i][j];
+            d.mi[i][j] = s.mi[i][j];
+        }
+        for (int x = 0; x < Dst::kLW; ++x) d.log[i][x] = x < L ? s.log[i][x] : WEnt{0, 0};
+    }
+    d.nmsg = s.nmsg;
+    d.pad[0] = d.pad[1] = 0;
+    for (int q = 0; q < Dst::kKW; ++q) {
+        typename Dst::Msg& m = d.msg[q];
+        if (q >= K) {
+            d.cnt[q] = 0;
+            wmsg_zero(m);
+            continue;
+        }
+        const typename Src::Msg& o = s.msg[q];
+        d.cnt[q] = s.cnt[q];
+        m.type = o.type;
+        m.term = o.term;
+        m.src = o.src;
+        m.dst = o.dst;
+        m.a = o.a;
+        m.b = o.b;
+        m.c = o.c;
+        m.n = o.n;
+        for (int x = 0; x < Dst::kLW; ++x) m.e[x] = x < L ? o.e[x] : WEnt{0, 0};
+    }
+}
+template <class St>
+RMC_HD void wconvert(St& d, const St& s) { wcopy_state(d, s); }
+
 RMC_HD int wquorum(const WModel& M, unsigned set) { return 2 * __builtin_popcount(set) > M.S; }  // raft.tla:81
 template <class St>
 RMC_HD int wlast_term(const St& s, int i) { return s.len[i] ? s.log[i][s.len[i] - 1].term : 0; }  // :84

@@ -188,6 +188,13 @@ struct WideBufs {
     u64 tmask, cap;
     Counters* ctr;
     u64 salt;         // fingerprint salt (rmc_config.seed)
+    // ring window (RMC_FLAG_SPILL): the store holds state i at slot i % window, the
+    // last `window` records (any size, no power of two); parent / act stay indexed
+    // by the state's index and cap stays "all states".  0: no ring, slot = index.
+    u64 window;
+    int work;         // ring: the record the expansion works on (>= the store's; same numbering)
+    int unstored;     // ring, per launch: the level being built is never expanded (max_depth):
+                      // its states get index, links and the invariant check, no record
 };
 // One successor listed by k_wlist (rmc_expand on the wide layout).
 struct WSucc {
@@ -196,7 +203,7 @@ struct WSucc {
     u64 fp;
     WState state;
 };
-hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st);  // B's layout
+hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st);  // staged: B's work record (ring) / store record
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st);
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st);

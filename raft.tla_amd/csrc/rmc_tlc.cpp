@@ -161,8 +161,11 @@ int usage() {
             "  -depth N   stop after N BFS levels (level N is left on the queue)\n"
             "  -verify    full-state verification: compare every fingerprint hit with the stored state\n"
             "  -nospill   keep every state on the device (stop with a capacity error when it fills);\n"
-            "             by default expanded levels spill to pinned host memory (single GPU)\n"
-            "  -window N  states kept on the device when spilling (default: what the set leaves)\n"
+            "             by default expanded levels leave the device window (single GPU; their trace\n"
+            "             links stay in HBM, or move to pinned host memory).  Runs on the wide layout\n"
+            "             (-depth runs of models with unbounded fields) spill too, unless -verify\n"
+            "  -window N  states kept on the device when spilling (default: what the set leaves;\n"
+            "             the wide layout keeps exactly N records, the packed one rounds up to 2^k)\n"
             "  -fpseed S  fingerprint salt (TLC -fp: another member of the fingerprint family)\n"
             "  -fpmem B   bytes of HBM for the fingerprint set (TLC -fpmem; suffix K/M/G; it holds\n"
             "             B / 16 states, \"fingerprint set full\" past that); default: sized for the\n"
@@ -299,10 +302,13 @@ int main(int argc, char** argv) {
     if (nodeadlock) c.flags &= ~RMC_FLAG_CHECK_DEADLOCK;
     if (verify) c.flags |= RMC_FLAG_VERIFY_STATES;
     // like TLC's states/ directory, expanded levels leave the device when it fills
-    // (single GPU, packed layout; under -verify the spilled states keep a host copy
-    // for the comparisons, and checkpoints of such runs stay resident; the wide
-    // layout of -depth runs of unbounded models has no spill)
-    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && rmc_state_bytes(&c) <= 64 * 4)
+    // (single GPU; under -verify the spilled states keep a host copy for the
+    // comparisons, and checkpoints of such runs stay resident).  The wide layout of
+    // -depth runs of unbounded models spills too, through a ring window of its
+    // records with the trace links in HBM — not under -verify, which it refuses
+    // with or without spill
+    const bool wide = rmc_state_bytes(&c) > 64 * 4;  // (a packed state is at most 18 words)
+    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && verify))
         c.flags |= RMC_FLAG_SPILL;
     c.device_window = window;
     c.set_bytes = fpmem;

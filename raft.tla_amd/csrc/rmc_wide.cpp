@@ -35,8 +35,8 @@ int validate_wide(const rmc_config* c, std::string* why) {
     if (c->max_log_len < 0 || c->max_log_len > RMC_WIDE_MAX_LOG) return bad("max_log_len must be 0..32 (wide layout)");
     if (c->max_msgs < 0 || c->max_msgs > RMC_WIDE_MAX_MSGS) return bad("max_msgs must be 0..64 (wide layout)");
     if (c->max_dup < 1 || c->max_dup > RMC_WIDE_MAX_DUP) return bad("max_dup must be 1..255 (wide layout)");
-    if (c->flags & (RMC_FLAG_SYMMETRY | RMC_FLAG_VERIFY_STATES | RMC_FLAG_SPILL))
-        return bad("the wide layout (bounds beyond the packed capacity) supports no SYMMETRY, verification or spill");
+    if (c->flags & (RMC_FLAG_SYMMETRY | RMC_FLAG_VERIFY_STATES))
+        return bad("the wide layout (bounds beyond the packed capacity) supports no SYMMETRY or verification");
     return 0;
 }
 
@@ -65,9 +65,7 @@ int wide_family(const rmc_ctx* c, int lane) { return lane == 255 ? -1 : c->WM.L.
 // and the bag at most n - 1 messages: raft_wide.h), 1: the compact WStateC (16,
 // 16; one step adds at most one entry and one message), 0: the full WState.
 // RMC_WIDE_COMPACT=0/1/2 overrides (A/B, tests).
-static int wide_compact(const rmc_config& g) {
-    if (const char* e = getenv("RMC_WIDE_COMPACT")) return std::max(0, std::min(2, atoi(e)));
-    const int steps = g.max_depth > 0 ? g.max_depth - 1 : 1 << 30;
+static int record_for(const rmc_config& g, int steps) {
     const bool blog = (g.flags & RMC_FLAG_UNBOUNDED_LOG) == 0, bmsg = (g.flags & RMC_FLAG_UNBOUNDED_MSGS) == 0;
     const int lead = (g.flags & RMC_FLAG_BUG_QUORUM) ? 5 : 9;  // steps before a first log entry can exist
     if (((blog && g.max_log_len <= LWD) || steps - lead <= LWD) && ((bmsg && g.max_msgs <= KWD) || steps - 1 <= KWD))
@@ -76,10 +74,39 @@ static int wide_compact(const rmc_config& g) {
     const bool msgs = (bmsg && g.max_msgs <= KWC) || steps <= KWC;
     return logs && msgs ? 1 : 0;
 }
+// With RMC_FLAG_SPILL (the ring window) a depth-bounded run never stores its
+// last level — it is never expanded — so the stored states are at most
+// max_depth - 2 steps from Init, one step fewer than above, and the expansion
+// works on a second, possibly larger record (WideBufs.work) that holds the
+// last level's states, max_depth - 1 steps: MCraft.cfg as shipped at depth 15
+// stores 336-B records and builds level 15 in 904-B ones.  RMC_WIDE_WORK=0/1/2
+// overrides the work record (never smaller than the store's).
+static int wide_compact(const rmc_config& g) {
+    if (const char* e = getenv("RMC_WIDE_COMPACT")) return std::max(0, std::min(2, atoi(e)));
+    const bool ring = (g.flags & RMC_FLAG_SPILL) != 0;
+    return record_for(g, g.max_depth > 0 ? g.max_depth - (ring ? 2 : 1) : 1 << 30);
+}
+static int wide_work(const rmc_config& g, int store) {
+    if (!(g.flags & RMC_FLAG_SPILL)) return store;
+    int w = record_for(g, g.max_depth > 0 ? g.max_depth - 1 : 1 << 30);
+    if (const char* e = getenv("RMC_WIDE_WORK")) w = std::max(0, std::min(2, atoi(e)));
+    return std::min(w, store);  // (0 is the largest record)
+}
 static size_t record_bytes(int kind) {
     return kind == 2 ? sizeof(WStateD) : kind == 1 ? sizeof(WStateC) : sizeof(WState);
 }
 size_t wide_record_bytes(const rmc_config& g) { return record_bytes(wide_compact(g)); }
+
+// The most new states one state's expansion can yield (rmc_api.cpp
+// max_new_per_state, the guards of raft.tla's Next) with the wide bag: per
+// server Restart + Timeout, or + S x RequestVote + BecomeLeader, or Restart +
+// V x ClientRequest + AdvanceCommitIndex + (S - 1) x AppendEntries, plus Receive,
+// Duplicate and Drop per message of a bag in the model and in the work record.
+static u64 wide_new_per_state(const rmc_config& g, int work) {
+    const u64 S = (u64)g.n_servers, V = (u64)g.n_values;
+    const u64 kw = work == 2 ? KWD : work == 1 ? KWC : KW;
+    return S * std::max<u64>(std::max<u64>(2, S + 3), S + V + 1) + 3 * std::min<u64>((u64)g.max_msgs, kw);
+}
 
 // ---- codec ----------------------------------------------------------------------
 int encode_wide(const rmc_ctx* c, const rmc_state_view& v, WState* out, std::string* why) {
@@ -235,33 +262,60 @@ int create_wide(rmc_ctx* c) {
     fill_wide_model(c);
     const int compact = wide_compact(c->cfg);
     const u64 rec = record_bytes(compact);
+    const bool ring = (c->cfg.flags & RMC_FLAG_SPILL) != 0;
     const u64 per_state = rec + 8 + 1;
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
     const u64 budget = (u64)((double)fr * 0.80);
-    const u64 set_slots = set_slots_of(c->cfg.set_bytes);  // rmc_config.set_bytes (TLC -fpmem)
+    u64 set_slots = set_slots_of(c->cfg.set_bytes);  // rmc_config.set_bytes (TLC -fpmem)
     u64 cap = c->cfg.state_capacity;
+    if (ring && set_slots && cap) {
+        // as on the packed layout, set_bytes is an upper bound: halved (down to load
+        // 1/2) until the links of every state and the window fit beside the set
+        const u64 need_win = c->cfg.device_window ? c->cfg.device_window : cap / 4;
+        while (set_slots > 1024 && set_slots / 2 >= 2 * cap && set_slots * 8 + cap * 9 + need_win * rec > budget)
+            set_slots >>= 1;
+    }
     if (set_slots && cap > set_slots / 2) {
         c->err = "state_capacity exceeds what a set of set_bytes " + std::to_string(c->cfg.set_bytes) + " holds";
         return RMC_E_INVAL;
     }
-    if (cap == 0)
+    if (cap == 0 && ring) {
+        // state_capacity sizes the set and the links only: what the given set holds,
+        // else the largest set of at most half the budget, two slots per state
+        u64 sl = 1ull << 20;
+        while (sl * 16 <= budget / 2) sl <<= 1;
+        cap = set_slots ? set_slots / 2 : sl / 2;
+    } else if (cap == 0) {
         cap = set_slots ? std::min<u64>(set_slots / 2, (budget - std::min<u64>(budget, set_slots * 8)) / per_state)
                         : budget / (per_state + 32);
+    }
     cap = std::max<u64>(std::min<u64>(cap, 1ull << 33), 1024);
     u64 slots = 1;
     while (slots < 2 * cap) slots <<= 1;
     if (set_slots) slots = std::max(slots, set_slots);
     c->table_slots = slots;
+    // the ring window: device_window records exactly (no rounding to a power of
+    // two: at 336 B to 5 KB a record, the round-up could cost tens of GB), or what
+    // the budget leaves after the set and the links, at most every state
+    u64 win = cap;
+    if (ring) {
+        const u64 fixed = slots * 8 + cap * 9;
+        win = c->cfg.device_window ? c->cfg.device_window : (budget - std::min<u64>(budget, fixed)) / rec;
+        win = std::max<u64>(std::min<u64>(win, cap), 1024);
+    }
     WideBufs& B = c->WB;
     B = WideBufs{};
     B.cap = cap;
     B.tmask = slots - 1;
     B.compact = compact;
-    if (hipMalloc(&B.store, cap * rec) != hipSuccess || hipMalloc(&B.parent, cap * 8) != hipSuccess ||
+    B.work = wide_work(c->cfg, compact);
+    B.window = ring ? win : 0;
+    if (hipMalloc(&B.store, win * rec) != hipSuccess || hipMalloc(&B.parent, cap * 8) != hipSuccess ||
         hipMalloc(&B.act, cap) != hipSuccess || hipMalloc(&B.table, slots * 8) != hipSuccess ||
         hipMalloc(&B.ctr, sizeof(Counters)) != hipSuccess || hipMalloc(&c->w_staged, sizeof(WState)) != hipSuccess)
-        return fail(c, RMC_E_NOMEM, "device allocation failed (wide layout, capacity " + std::to_string(cap) + " states)");
+        return fail(c, RMC_E_NOMEM, "device allocation failed (wide layout, capacity " + std::to_string(cap) +
+                                        " states" + (ring ? ", window " + std::to_string(win) + " records" : "") + ")");
     c->B.ctr = B.ctr;  // reset_counters / read_counters work on it
     c->B.cap = cap;
     return 0;
@@ -292,18 +346,21 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->have_target = 0;
     c->res = rmc_result{};
     c->res.set_slots = c->table_slots;
+    c->res.spill_links_on_device = B.window ? 1 : 0;
     c->level_start.clear();
     HIPCHK(c, launch_fill(B.table, c->table_slots * 8, 0, c->st));
     c->h_ctr->count = 0;
     if (int rc = reset_counters(c, false)) return rc;
+    // Init in the record the seed kernel reads: the work record (= the store's without the ring)
+    const int seed_rec = B.window ? B.work : B.compact;
     WState init;
     WStateC initc;
     WStateD initd;
     winit(c->WM, init);
     winit(c->WM, initc);
     winit(c->WM, initd);
-    if (B.compact == 2) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initd, sizeof initd, hipMemcpyHostToDevice, c->st));
-    else if (B.compact) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initc, sizeof initc, hipMemcpyHostToDevice, c->st));
+    if (seed_rec == 2) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initd, sizeof initd, hipMemcpyHostToDevice, c->st));
+    else if (seed_rec) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initc, sizeof initc, hipMemcpyHostToDevice, c->st));
     else HIPCHK(c, hipMemcpyAsync(c->w_staged, &init, sizeof init, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging copies live on this stack frame)
     HIPCHK(c, launch_wseed(c->WM, B, c->w_staged, 1, c->st));
@@ -319,6 +376,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         c->target_idx = c->h_ctr->viol >> 4;
     }
     const u64 CHUNK = 1ull << 22;
+    const u64 bound = wide_new_per_state(c->cfg, B.work);
+    u64 records = c->h_ctr->count;  // ring: records written so far
     while (!c->have_target) {
         const u64 lo = c->level_start[(size_t)depth - 1], hi = c->level_start[(size_t)depth];
         if (lo == hi) break;
@@ -328,9 +387,43 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         }
         if (int rc = reset_counters(c, true)) return rc;
         HIPCHK(c, hipEventRecord(c->ev0, c->st));
-        for (u64 a = lo; a < hi; a += CHUNK) {
-            HIPCHK(c, launch_wexpand(c->WM, B, a, std::min(hi, a + CHUNK), c->st));
+        // the ring: a level no later one expands (max_depth) is not stored, and its
+        // launches need no room
+        B.unstored = B.window && c->cfg.max_depth > 0 && depth == c->cfg.max_depth - 1;
+        for (u64 a = lo, b = 0; a < hi; a = b) {
+            b = std::min(hi, a + CHUNK);
+            if (B.window && !B.unstored) {
+                // [a, count) is live (the rest of the frontier and the level being
+                // built); a state yields at most `bound` new states, so a launch of n
+                // states overwrites no live record when count + n * bound <= a + window
+                const u64 count = c->h_ctr->count, win = B.window;
+                const u64 room = count - a < win ? a + win - count : 0;
+                const u64 want = std::min(b - a, room / bound);
+                if (want == 0)
+                    return fail(c, RMC_E_CAPACITY,
+                                "spill: the device window (" + std::to_string(win) +
+                                    " states) cannot hold the frontier and the level being built; raise "
+                                    "rmc_config.device_window, or give the fingerprint set less HBM "
+                                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
+                                    std::to_string(c->table_slots) + " slots take " +
+                                    std::to_string((c->table_slots * 8) >> 30) + " GiB) so the window gets more");
+                b = a + want;
+            }
+            HIPCHK(c, launch_wexpand(c->WM, B, a, b, c->st));
             c->res.expand_launches += 1;
+            if (B.window) {
+                const u64 before = c->h_ctr->count;
+                if (int rc = read_counters(c)) return rc;
+                if (c->h_ctr->overflow || c->h_ctr->table_full) break;
+                // the room above rests on the bound: checked, not trusted
+                if (c->h_ctr->count - before > (b - a) * bound)
+                    return fail(c, RMC_E_HIP, "ring bound exceeded: " + std::to_string(b - a) + " states yielded " +
+                                                  std::to_string(c->h_ctr->count - before) + " new states, bound " +
+                                                  std::to_string(bound) + " each");
+                if (!B.unstored) records = c->h_ctr->count;
+                c->res.spilled = records > B.window ? records - B.window : 0;
+                c->res.spills = records / B.window;  // passes of the ring
+            }
         }
         HIPCHK(c, hipEventRecord(c->ev1, c->st));
         if (int rc = read_counters(c)) return rc;
@@ -401,6 +494,25 @@ int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* i
     std::reverse(chain.begin(), chain.end());
     std::reverse(acts.begin(), acts.end());
     *len = chain.size();
+    if (c->WB.window) {
+        // the ring: a state of the chain may be overwritten, or of the unstored last
+        // level — every state is re-derived from Init by its lane, on full records
+        // (a bag lane is a slot of the parent's canonical bag, the same in every record)
+        WState s, t;
+        winit(c->WM, s);
+        for (size_t q = 0; q < chain.size() && q < cap; ++q) {
+            if (q) {
+                if (wlane(c->WM, s, (int)acts[q], &t) != W_ON)
+                    return fail(c, RMC_E_HIP, "trace replay: lane " + std::to_string((int)acts[q]) + " of state " +
+                                                  std::to_string(chain[q - 1]) + " gives no successor");
+                wcopy_state(s, t);
+            }
+            if (states) decode_wide(c, s, &states[q]);
+            if (families) families[q] = wide_family(c, acts[q]);
+            if (instances) instances[q] = acts[q] == 255 ? -1 : acts[q];
+        }
+        return 0;
+    }
     for (size_t q = 0; q < chain.size() && q < cap; ++q) {
         if (c->WB.compact == 2) {
             WStateD s;

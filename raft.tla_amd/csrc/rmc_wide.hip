@@ -7,6 +7,8 @@
 // same kind of open-addressing HBM set as the packed kernels use.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "raft_wide.h"
 #include "rmc_internal.h"
 
@@ -38,21 +40,39 @@ __device__ __forceinline__ u64 w_wave_sum(u64 v) {
     return v;
 }
 
-// Store a new state (slot allocated by the caller) with its trace link and the
-// fused invariant check.
-template <class St>
-__device__ __forceinline__ void w_store(const WModel& M, const WideBufs& B, u64 ni, const St& t, u64 parent,
-                                        int lane) {
-    wcopy_state(static_cast<St*>(B.store)[ni], t);
+// The slot of state i's record: its index, or in the ring window i % window
+// (any size; one 64-bit remainder per 336-B to 5-KB record copy).
+template <bool Ring>
+__device__ __forceinline__ u64 w_slot(const WideBufs& B, u64 i) {
+    return Ring ? i % B.window : i;
+}
+
+// Store a new state (index allocated by the caller) with its trace link and the
+// fused invariant check on the caller's private copy.  Ring: t is narrowed into
+// the store's record — one it does not fit is never cut short: the fields come
+// back as Counters.overflow field bits and nothing is written — and a state of
+// a level that is never expanded (B.unstored) gets no record at all.
+template <class Store, bool Ring, class Work>
+__device__ __forceinline__ u32 w_store(const WModel& M, const WideBufs& B, u64 ni, const Work& t, u64 parent,
+                                       int lane) {
+    u32 bad = 0;
+    if (!Ring) {
+        wcopy_state(static_cast<Work*>(B.store)[ni], t);
+    } else if (!B.unstored) {
+        bad = (u32)wnarrow_bits<Store>(t);
+        if (!bad) wconvert(static_cast<Store*>(B.store)[w_slot<Ring>(B, ni)], t);
+    }
     B.parent[ni] = parent;
     B.act[ni] = (uint8_t)lane;
     const int v = wcheck_invariants(M, t);
     if (v) atomicMin((unsigned long long*)&B.ctr->viol, (unsigned long long)((ni << 4) | (u64)(v - 1)));
+    return bad;
 }
 
-// Init (raft.tla:125-129) or SmokeInit's states: n staged records.
-template <class St>
-__global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B, const St* staged, u64 n) {
+// Init (raft.tla:125-129) or SmokeInit's states: n staged records (of the work type).
+template <class Store, class Work, bool Ring>
+__global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B, const Work* staged, u64 n) {
+    static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
     for (u64 t = (u64)blockIdx.x * 256ull + threadIdx.x; t < n; t += (u64)gridDim.x * 256ull) {
         if (!w_insert(B.table, B.tmask, wfp(staged[t], B.salt, M.S), &B.ctr->table_full)) continue;
         const u64 ni = atomicAdd((unsigned long long*)&B.ctr->count, 1ull);
@@ -60,7 +80,8 @@ __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B,
             atomicOr(&B.ctr->overflow, 1u);
             continue;
         }
-        w_store(M, B, ni, staged[t], ~0ull, 255);
+        const u32 bad = w_store<Store, Ring>(M, B, ni, staged[t], ~0ull, 255);
+        if (bad) atomicOr(&B.ctr->overflow, bad << 8);
     }
 }
 
@@ -71,14 +92,20 @@ __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B,
 // once per state and each successor's from it (wfp_delta: the components the
 // lane changed), the bag families walked only over the state's messages, and
 // stuttering successors (the parent's fingerprint) not probed.
-template <class St>
+// Ring (RMC_FLAG_SPILL): the frontier state is read from its ring slot and
+// widened into a Work record; lanes, CONSTRAINT and fingerprints run on Work
+// (wfp does not depend on the record's capacity), and a stored successor is
+// narrowed into a Store record (w_store).
+template <class Store, class Work, bool Ring>
 __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs B, u64 lo, u64 hi) {
+    static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
+    static_assert(Store::kLW <= Work::kLW && Store::kKW <= Work::kKW, "the work record holds every stored state");
     u64 gen = 0, probes = 0;
     u32 bad = 0;
     const int o7 = M.L.off[7];
     for (u64 i = lo + (u64)blockIdx.x * 256ull + threadIdx.x; i < hi; i += (u64)gridDim.x * 256ull) {
-        St s, t;
-        wcopy_state(s, static_cast<const St*>(B.store)[i]);
+        Work s, t;
+        wconvert(s, static_cast<const Store*>(B.store)[w_slot<Ring>(B, i)]);
         const Fp h0 = wfp(s, B.salt, M.S);
         u32 g = 0;
         // lanes of families 0-6, then the three bag families over slots [0, nmsg)
@@ -103,7 +130,7 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
                 atomicOr(&B.ctr->overflow, 1u);
                 continue;
             }
-            w_store(M, B, ni, t, i, lane);
+            bad |= w_store<Store, Ring>(M, B, ni, t, i, lane);
         }
         if (g == 0) atomicMin((unsigned long long*)&B.ctr->deadlock, (unsigned long long)i);
         gen += g;
@@ -437,28 +464,49 @@ static unsigned grid_for(u64 n, u64 threads, u64 maxg) {
     return (unsigned)(b < maxg ? (b ? b : 1) : maxg);
 }
 
+// The record pairs <store, work> of a ctx (WideBufs.compact / .work: 0 WState,
+// 1 WStateC, 2 WStateD): without the ring the store's record on both sides
+// (the three kernels of round 6), with it every pair whose work record is no
+// smaller than the store's.
+template <class F>
+static bool w_dispatch(const WideBufs& B, F f) {
+    if (!B.window) {
+        if (B.compact == 2) f((WStateD*)nullptr, (WStateD*)nullptr, std::false_type{});
+        else if (B.compact) f((WStateC*)nullptr, (WStateC*)nullptr, std::false_type{});
+        else f((WState*)nullptr, (WState*)nullptr, std::false_type{});
+        return true;
+    }
+    const int p = B.compact * 3 + B.work;
+    switch (p) {
+        case 2 * 3 + 2: f((WStateD*)nullptr, (WStateD*)nullptr, std::true_type{}); return true;
+        case 2 * 3 + 1: f((WStateD*)nullptr, (WStateC*)nullptr, std::true_type{}); return true;
+        case 2 * 3 + 0: f((WStateD*)nullptr, (WState*)nullptr, std::true_type{}); return true;
+        case 1 * 3 + 1: f((WStateC*)nullptr, (WStateC*)nullptr, std::true_type{}); return true;
+        case 1 * 3 + 0: f((WStateC*)nullptr, (WState*)nullptr, std::true_type{}); return true;
+        case 0: f((WState*)nullptr, (WState*)nullptr, std::true_type{}); return true;
+    }
+    return false;  // a work record smaller than the store's: no such kernel
+}
+
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st) {
     if (!n) return hipSuccess;
-    if (B.compact == 2)
-        hipLaunchKernelGGL(k_wseed<WStateD>, dim3(grid_for(n, 256, 1024)), dim3(256), 0, st, M, B,
-                           static_cast<const WStateD*>(staged), n);
-    else if (B.compact)
-        hipLaunchKernelGGL(k_wseed<WStateC>, dim3(grid_for(n, 256, 1024)), dim3(256), 0, st, M, B,
-                           static_cast<const WStateC*>(staged), n);
-    else
-        hipLaunchKernelGGL(k_wseed<WState>, dim3(grid_for(n, 256, 1024)), dim3(256), 0, st, M, B,
-                           static_cast<const WState*>(staged), n);
-    return hipGetLastError();
+    const bool ok = w_dispatch(B, [&](auto* sp, auto* wp, auto ring) {
+        typedef std::remove_pointer_t<decltype(sp)> Store;
+        typedef std::remove_pointer_t<decltype(wp)> Work;
+        hipLaunchKernelGGL((k_wseed<Store, Work, decltype(ring)::value>), dim3(grid_for(n, 256, 1024)), dim3(256), 0, st,
+                           M, B, static_cast<const Work*>(staged), n);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st) {
     if (hi <= lo) return hipSuccess;
-    if (B.compact == 2)
-        hipLaunchKernelGGL(k_wexpand<WStateD>, dim3(grid_for(hi - lo, 256, 4096)), dim3(256), 0, st, M, B, lo, hi);
-    else if (B.compact)
-        hipLaunchKernelGGL(k_wexpand<WStateC>, dim3(grid_for(hi - lo, 256, 4096)), dim3(256), 0, st, M, B, lo, hi);
-    else
-        hipLaunchKernelGGL(k_wexpand<WState>, dim3(grid_for(hi - lo, 256, 4096)), dim3(256), 0, st, M, B, lo, hi);
-    return hipGetLastError();
+    const bool ok = w_dispatch(B, [&](auto* sp, auto* wp, auto ring) {
+        typedef std::remove_pointer_t<decltype(sp)> Store;
+        typedef std::remove_pointer_t<decltype(wp)> Work;
+        hipLaunchKernelGGL((k_wexpand<Store, Work, decltype(ring)::value>), dim3(grid_for(hi - lo, 256, 4096)), dim3(256),
+                           0, st, M, B, lo, hi);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st) {

@@ -5,7 +5,10 @@ cumulative seconds and rate; the deepest bound one GPU completes; the record
 size the front-end picked (336-B depth-sized up to depth 14, 904-B compact up to
 depth 17).  Measurement tool.
 
-    python tools/mcraft_shipped.py MAX_DEPTH [record: auto|full|compact|depth] > levels.jsonl
+    python tools/mcraft_shipped.py MAX_DEPTH [record: auto|full|compact|depth] [spill [CAPACITY]] > levels.jsonl
+
+spill: RMC_FLAG_SPILL (the ring window; the last level is not stored, so the record
+is sized one level shallower: 336 B to depth 15); CAPACITY sizes the set and the links.
 """
 import json
 import os
@@ -24,6 +27,9 @@ base, _, _ = rmc.model_from_files(os.path.join(ROOT, "tests", "golden", "models"
 c = rmc.Config.from_buffer_copy(base)
 c.max_depth = depth
 c.state_capacity = 0  # librmc's own sizing: 80 % of free HBM
+if len(sys.argv) > 3 and sys.argv[3] == "spill":
+    c.flags |= rmc.FLAG_SPILL
+    c.state_capacity = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 nbytes = rmc.native().rmc_state_bytes(c)
 
 

@@ -37,8 +37,13 @@ extern "C" {
 #define RMC_MAX_DUP 3      /* per-message count bound <= 3 */
 /* Capacity of the wide encoding (DESIGN.md "Wide state"): a model with any
  * bound beyond the packed capacity — or a field no CONSTRAINT bounds, under a
- * depth bound or in simulation — runs on it (single GPU; no SYMMETRY or
- * verification; RMC_FLAG_SPILL keeps its records in a ring window).  A
+ * depth bound or in simulation — runs on it (single GPU; no SYMMETRY;
+ * RMC_FLAG_SPILL keeps its records in a ring window; RMC_FLAG_VERIFY_STATES
+ * compares every fingerprint hit with the resident stored state, so the two
+ * flags together are RMC_E_INVAL: at the depths that need the ring — depth 15
+ * of MCraft.cfg as shipped, 2.24 G states, 2^33 set slots — the slot-to-state
+ * array of 8 B per slot no longer fits beside the set and the frontier; such a
+ * run is cross-checked by a second fingerprint salt, rmc_config.seed).  A
  * CONSTRAINT bound must stay below the wide capacity; an unbounded field is
  * given the capacity itself, and a successor beyond it stops the search with
  * RMC_E_CAPACITY naming the field. */
@@ -69,7 +74,9 @@ extern "C" {
 #define RMC_FLAG_VERIFY_STATES (1u << 3)   /* full-state verification: every fingerprint */
                                            /* hit is compared with the stored state;    */
                                            /* differences = collisions (no TLC analog;  */
-                                           /* single GPU)                               */
+                                           /* single GPU).  Both layouts; on the wide   */
+                                           /* one without RMC_FLAG_SPILL only (8 B more */
+                                           /* per set slot, every state resident)       */
 #define RMC_FLAG_SPILL (1u << 4)           /* frontier spill (TLC's states/ directory): */
                                            /* expanded levels leave the device window   */
                                            /* when it fills, so a model whose states    */
@@ -89,7 +96,8 @@ extern "C" {
                                            /* HBM; a run bounded by max_depth does not   */
                                            /* store its last level (never expanded), so  */
                                            /* its record is sized one level shallower;   */
-                                           /* traces are replayed from Init              */
+                                           /* traces are replayed from Init; not with    */
+                                           /* RMC_FLAG_VERIFY_STATES (RMC_E_INVAL)       */
 /* A model without a CONSTRAINT on some field (MCraft.cfg as shipped) runs only
  * under a depth bound (max_depth > 0, TLC -depth).  The front-end then gives
  * each unbounded field the wide capacity (RMC_WIDE_MAX_TERM, RMC_WIDE_MAX_LOG,

@@ -165,6 +165,15 @@ RMC_HD TKey tkey(const Fp& h, u64 mask) {
     const u32 s = fp_norm(h.k, h.s, mask);
     return TKey{fp_v(h.k, s, mask), h.k & mask};
 }
+// rmc_set_fp_bits (verification tests, both layouts): only the kept bits of k, no
+// second sum, so a weakened fingerprint collides as often as its width says.
+RMC_HD Fp fp_weaken(Fp h, u64 fp_mask) {
+    if (fp_mask != ~0ull) {
+        h.k &= fp_mask;
+        h.s = 0;
+    }
+    return h;
+}
 
 // Owner rank of a fingerprint in sharded mode: its top 32 bits scaled to
 // [0, world).  The fingerprint-set slot uses the low bits, so every shard's

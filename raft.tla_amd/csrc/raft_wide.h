@@ -215,6 +215,40 @@ RMC_HD void wconvert(Dst& d, const Src& s) {
 template <class St>
 RMC_HD void wconvert(St& d, const St& s) { wcopy_state(d, s); }
 
+// TLA+ equality of two canonical records of any two types (full-state
+// verification, RMC_FLAG_VERIFY_STATES): the ten variables field by field — per
+// server the scalars and the log up to its length, the vote sets, nextIndex and
+// matchIndex over the S servers, the bag's messages in order with their counts.
+// A length beyond the other record's capacity is a difference before any entry
+// is read, so neither record is read past its arrays, and a state narrowed by
+// wconvert equals its original.
+template <class A, class B>
+RMC_HD bool wsame(const A& a, const B& b, int S = WS) {
+    constexpr int L = A::kLW < B::kLW ? A::kLW : B::kLW, K = A::kKW < B::kKW ? A::kKW : B::kKW;
+    if (a.nmsg != b.nmsg || a.nmsg > K) return false;
+    for (int i = 0; i < S; ++i) {
+        if (a.ct[i] != b.ct[i] || a.st[i] != b.st[i] || a.vf[i] != b.vf[i] || a.ci[i] != b.ci[i] ||
+            a.len[i] != b.len[i] || a.vR[i] != b.vR[i] || a.vG[i] != b.vG[i])
+            return false;
+        if (a.len[i] > L) return false;
+        for (int x = 0; x < a.len[i]; ++x)
+            if (a.log[i][x].term != b.log[i][x].term || a.log[i][x].value != b.log[i][x].value) return false;
+        for (int j = 0; j < S; ++j)
+            if (a.ni[i][j] != b.ni[i][j] || a.mi[i][j] != b.mi[i][j]) return false;
+    }
+    for (int q = 0; q < a.nmsg; ++q) {
+        const typename A::Msg& m = a.msg[q];
+        const typename B::Msg& o = b.msg[q];
+        if (a.cnt[q] != b.cnt[q] || m.type != o.type || m.term != o.term || m.src != o.src || m.dst != o.dst ||
+            m.a != o.a || m.b != o.b || m.c != o.c || m.n != o.n)
+            return false;
+        if (m.n > L) return false;
+        for (int x = 0; x < m.n; ++x)
+            if (m.e[x].term != o.e[x].term || m.e[x].value != o.e[x].value) return false;
+    }
+    return true;
+}
+
 RMC_HD int wquorum(const WModel& M, unsigned set) { return 2 * __builtin_popcount(set) > M.S; }  // raft.tla:81
 template <class St>
 RMC_HD int wlast_term(const St& s, int i) { return s.len[i] ? s.log[i][s.len[i] - 1].term : 0; }  // :84

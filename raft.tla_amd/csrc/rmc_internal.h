@@ -195,6 +195,18 @@ struct WideBufs {
     int work;         // ring: the record the expansion works on (>= the store's; same numbering)
     int unstored;     // ring, per launch: the level being built is never expanded (max_depth):
                       // its states get index, links and the invariant check, no record
+    // full-state verification (RMC_FLAG_VERIFY_STATES; resident store only): the
+    // store index of the state owning each set slot (~0: none yet), written by the
+    // inserting lane itself, and the hits of a launch on owners found in the same
+    // launch {parent index, slot | lane << 48}, compared by k_wverify after it (a
+    // lane needs 9 bits, a slot index is below 2^34).  The tallies are Counters'
+    // collisions / vchecked / vcount.  verify = 0: none of these is read.
+    int verify;
+    u64* sidx;
+    u64* vbuf;
+    u64 vcap;         // records in vbuf
+    u64 vbase;        // per launch: Counters.count when it began (owners at or above it are deferred)
+    u64 fp_mask;      // fingerprint bits kept (~0 = all; rmc_set_fp_bits)
 };
 // One successor listed by k_wlist (rmc_expand on the wide layout).
 struct WSucc {
@@ -205,6 +217,7 @@ struct WSucc {
 };
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st);  // staged: B's work record (ring) / store record
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st);
+hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t st);  // the n deferred hits in B.vbuf
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,

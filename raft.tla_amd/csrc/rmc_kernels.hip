@@ -100,15 +100,7 @@ __device__ __forceinline__ int fp_insert_fp(u64* __restrict__ table, u64 mask, c
     const TKey t = tkey(h, mask);
     return fp_insert(table, mask, t.s0, t.v, full);
 }
-// rmc_set_fp_bits (verification tests): only the kept bits of k, no second sum,
-// so a weakened fingerprint collides as often as its width says.
-__device__ __forceinline__ Fp fp_weaken(Fp h, u64 fp_mask) {
-    if (fp_mask != ~0ull) {
-        h.k &= fp_mask;
-        h.s = 0;
-    }
-    return h;
-}
+// (fp_weaken, the rmc_set_fp_bits hook: raft_packed.h, shared with rmc_wide.hip)
 
 template <int S, int K>
 __device__ __forceinline__ void load_state(const u32* __restrict__ base, u64 (&w)[S], u32 (&m)[K]) {

@@ -160,6 +160,8 @@ int usage() {
             "  -builtin-raft  no raft.tla on disk: check the compiled-in lemmy/raft.tla (said in the output)\n"
             "  -depth N   stop after N BFS levels (level N is left on the queue)\n"
             "  -verify    full-state verification: compare every fingerprint hit with the stored state\n"
+            "             and report the collisions (both layouts; a wide-layout run then keeps every\n"
+            "             state on the device, as under -nospill)\n"
             "  -nospill   keep every state on the device (stop with a capacity error when it fills);\n"
             "             by default expanded levels leave the device window (single GPU; their trace\n"
             "             links stay in HBM, or move to pinned host memory).  Runs on the wide layout\n"
@@ -305,8 +307,8 @@ int main(int argc, char** argv) {
     // (single GPU; under -verify the spilled states keep a host copy for the
     // comparisons, and checkpoints of such runs stay resident).  The wide layout of
     // -depth runs of unbounded models spills too, through a ring window of its
-    // records with the trace links in HBM — not under -verify, which it refuses
-    // with or without spill
+    // records with the trace links in HBM — not under -verify, which on the wide
+    // layout compares with resident records only (it refuses the two flags together)
     const bool wide = rmc_state_bytes(&c) > 64 * 4;  // (a packed state is at most 18 words)
     if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && verify))
         c.flags |= RMC_FLAG_SPILL;

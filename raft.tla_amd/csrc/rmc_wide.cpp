@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rmc_ctx.h"
+#include "rmc_wide_plan.h"
 
 using namespace rmc;
 using namespace rmc::wide;
@@ -35,8 +36,14 @@ int validate_wide(const rmc_config* c, std::string* why) {
     if (c->max_log_len < 0 || c->max_log_len > RMC_WIDE_MAX_LOG) return bad("max_log_len must be 0..32 (wide layout)");
     if (c->max_msgs < 0 || c->max_msgs > RMC_WIDE_MAX_MSGS) return bad("max_msgs must be 0..64 (wide layout)");
     if (c->max_dup < 1 || c->max_dup > RMC_WIDE_MAX_DUP) return bad("max_dup must be 1..255 (wide layout)");
-    if (c->flags & (RMC_FLAG_SYMMETRY | RMC_FLAG_VERIFY_STATES))
-        return bad("the wide layout (bounds beyond the packed capacity) supports no SYMMETRY or verification");
+    if (c->flags & RMC_FLAG_SYMMETRY)
+        return bad("the wide layout (bounds beyond the packed capacity) supports no SYMMETRY");
+    // verification compares a hit with its owner's resident record, found through 8 B
+    // more per set slot; at the depths that need the ring that array no longer fits
+    // beside the set and the window (DESIGN.md "Wide state")
+    if ((c->flags & RMC_FLAG_VERIFY_STATES) && (c->flags & RMC_FLAG_SPILL))
+        return bad("the wide layout (bounds beyond the packed capacity) supports RMC_FLAG_VERIFY_STATES only "
+                   "without RMC_FLAG_SPILL: verification needs every state resident");
     return 0;
 }
 
@@ -102,10 +109,13 @@ size_t wide_record_bytes(const rmc_config& g) { return record_bytes(wide_compact
 // server Restart + Timeout, or + S x RequestVote + BecomeLeader, or Restart +
 // V x ClientRequest + AdvanceCommitIndex + (S - 1) x AppendEntries, plus Receive,
 // Duplicate and Drop per message of a bag in the model and in the work record.
+static u64 wide_bag(const rmc_config& g, int work) {  // messages of a stored state at most
+    const u64 kw = work == 2 ? KWD : work == 1 ? KWC : KW;
+    return std::min<u64>((u64)g.max_msgs, kw);
+}
 static u64 wide_new_per_state(const rmc_config& g, int work) {
     const u64 S = (u64)g.n_servers, V = (u64)g.n_values;
-    const u64 kw = work == 2 ? KWD : work == 1 ? KWC : KW;
-    return S * std::max<u64>(std::max<u64>(2, S + 3), S + V + 1) + 3 * std::min<u64>((u64)g.max_msgs, kw);
+    return S * std::max<u64>(std::max<u64>(2, S + 3), S + V + 1) + 3 * wide_bag(g, work);
 }
 
 // ---- codec ----------------------------------------------------------------------
@@ -258,52 +268,40 @@ void decode_wide(const rmc_ctx* c, const St& s, rmc_state_view* v) {
 }
 
 // ---- context ----------------------------------------------------------------------
+// Records of the deferred-hit buffer of full-state verification (WideBufs.vbuf): the
+// packed layout's default; RMC_WIDE_VCAP=<records> overrides (A/B, tests: a small
+// buffer makes many launches per level).
+static u64 wide_vcap() {
+    u64 v = 1ull << 26;
+    if (const char* e = getenv("RMC_WIDE_VCAP")) v = strtoull(e, nullptr, 10);
+    return std::max<u64>(std::min<u64>(v, 1ull << 32), 1024);  // (a state has at most WLANES_MAX = 272 lanes)
+}
+
 int create_wide(rmc_ctx* c) {
     fill_wide_model(c);
     const int compact = wide_compact(c->cfg);
     const u64 rec = record_bytes(compact);
     const bool ring = (c->cfg.flags & RMC_FLAG_SPILL) != 0;
-    const u64 per_state = rec + 8 + 1;
+    const bool verify = (c->cfg.flags & RMC_FLAG_VERIFY_STATES) != 0;
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
-    const u64 budget = (u64)((double)fr * 0.80);
-    u64 set_slots = set_slots_of(c->cfg.set_bytes);  // rmc_config.set_bytes (TLC -fpmem)
-    u64 cap = c->cfg.state_capacity;
-    if (ring && set_slots && cap) {
-        // as on the packed layout, set_bytes is an upper bound: halved (down to load
-        // 1/2) until the links of every state and the window fit beside the set
-        const u64 need_win = c->cfg.device_window ? c->cfg.device_window : cap / 4;
-        while (set_slots > 1024 && set_slots / 2 >= 2 * cap && set_slots * 8 + cap * 9 + need_win * rec > budget)
-            set_slots >>= 1;
-    }
-    if (set_slots && cap > set_slots / 2) {
+    // the division of the budget: rmc_wide_plan.h (host arithmetic, tested without a device)
+    WidePlanIn in{};
+    in.budget = (u64)((double)fr * 0.80);
+    in.rec = rec;
+    in.state_capacity = c->cfg.state_capacity;
+    in.set_slots = set_slots_of(c->cfg.set_bytes);  // rmc_config.set_bytes (TLC -fpmem)
+    in.device_window = c->cfg.device_window;
+    in.ring = ring;
+    in.verify = verify;
+    in.vcap = verify ? wide_vcap() : 0;
+    const WidePlan plan = wide_plan(in);
+    if (plan.cap_exceeds_set) {
         c->err = "state_capacity exceeds what a set of set_bytes " + std::to_string(c->cfg.set_bytes) + " holds";
         return RMC_E_INVAL;
     }
-    if (cap == 0 && ring) {
-        // state_capacity sizes the set and the links only: what the given set holds,
-        // else the largest set of at most half the budget, two slots per state
-        u64 sl = 1ull << 20;
-        while (sl * 16 <= budget / 2) sl <<= 1;
-        cap = set_slots ? set_slots / 2 : sl / 2;
-    } else if (cap == 0) {
-        cap = set_slots ? std::min<u64>(set_slots / 2, (budget - std::min<u64>(budget, set_slots * 8)) / per_state)
-                        : budget / (per_state + 32);
-    }
-    cap = std::max<u64>(std::min<u64>(cap, 1ull << 33), 1024);
-    u64 slots = 1;
-    while (slots < 2 * cap) slots <<= 1;
-    if (set_slots) slots = std::max(slots, set_slots);
+    const u64 cap = plan.cap, slots = plan.slots, win = plan.window;
     c->table_slots = slots;
-    // the ring window: device_window records exactly (no rounding to a power of
-    // two: at 336 B to 5 KB a record, the round-up could cost tens of GB), or what
-    // the budget leaves after the set and the links, at most every state
-    u64 win = cap;
-    if (ring) {
-        const u64 fixed = slots * 8 + cap * 9;
-        win = c->cfg.device_window ? c->cfg.device_window : (budget - std::min<u64>(budget, fixed)) / rec;
-        win = std::max<u64>(std::min<u64>(win, cap), 1024);
-    }
     WideBufs& B = c->WB;
     B = WideBufs{};
     B.cap = cap;
@@ -311,11 +309,20 @@ int create_wide(rmc_ctx* c) {
     B.compact = compact;
     B.work = wide_work(c->cfg, compact);
     B.window = ring ? win : 0;
+    B.verify = verify ? 1 : 0;
+    B.vcap = in.vcap;
+    B.fp_mask = ~0ull;
     if (hipMalloc(&B.store, win * rec) != hipSuccess || hipMalloc(&B.parent, cap * 8) != hipSuccess ||
         hipMalloc(&B.act, cap) != hipSuccess || hipMalloc(&B.table, slots * 8) != hipSuccess ||
-        hipMalloc(&B.ctr, sizeof(Counters)) != hipSuccess || hipMalloc(&c->w_staged, sizeof(WState)) != hipSuccess)
+        hipMalloc(&B.ctr, sizeof(Counters)) != hipSuccess || hipMalloc(&c->w_staged, sizeof(WState)) != hipSuccess ||
+        // verification: slot -> store index (8 B per slot) + the deferred hits (16 B each)
+        (verify && (hipMalloc(&B.sidx, slots * 8) != hipSuccess || hipMalloc(&B.vbuf, B.vcap * 16) != hipSuccess)))
         return fail(c, RMC_E_NOMEM, "device allocation failed (wide layout, capacity " + std::to_string(cap) +
-                                        " states" + (ring ? ", window " + std::to_string(win) + " records" : "") + ")");
+                                        " states" + (ring ? ", window " + std::to_string(win) + " records" : "") +
+                                        (verify ? ", verification: " + std::to_string(slots) + " slot owners and " +
+                                                      std::to_string(B.vcap) + " deferred hits"
+                                                : "") +
+                                        ")");
     c->B.ctr = B.ctr;  // reset_counters / read_counters work on it
     c->B.cap = cap;
     return 0;
@@ -328,6 +335,8 @@ void destroy_wide(rmc_ctx* c) {
     (void)hipFree(B.act);
     (void)hipFree(B.table);
     (void)hipFree(B.ctr);
+    (void)hipFree(B.sidx);
+    (void)hipFree(B.vbuf);
     (void)hipFree(c->w_staged);
     B = WideBufs{};
     c->B.ctr = nullptr;
@@ -349,6 +358,11 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->res.spill_links_on_device = B.window ? 1 : 0;
     c->level_start.clear();
     HIPCHK(c, launch_fill(B.table, c->table_slots * 8, 0, c->st));
+    if (B.verify) {  // no slot has an owner yet
+        HIPCHK(c, launch_fill(B.sidx, c->table_slots * 8, 0xFF, c->st));
+        B.fp_mask = c->P.fp_mask;  // rmc_set_fp_bits
+        B.vbase = 0;
+    }
     c->h_ctr->count = 0;
     if (int rc = reset_counters(c, false)) return rc;
     // Init in the record the seed kernel reads: the work record (= the store's without the ring)
@@ -378,6 +392,11 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const u64 CHUNK = 1ull << 22;
     const u64 bound = wide_new_per_state(c->cfg, B.work);
     u64 records = c->h_ctr->count;  // ring: records written so far
+    // verification: a launch defers at most one hit per lane of its states — the
+    // lanes of families 0-6 and three per message of a bag in the model and in the
+    // work record — so one of at most vcap / lanes states cannot overflow vbuf
+    const u64 vlanes = (u64)c->WM.L.off[7] + 3 * wide_bag(c->cfg, B.work);
+    const u64 chunk = B.verify ? std::max<u64>(1, std::min(CHUNK, B.vcap / vlanes)) : CHUNK;
     while (!c->have_target) {
         const u64 lo = c->level_start[(size_t)depth - 1], hi = c->level_start[(size_t)depth];
         if (lo == hi) break;
@@ -391,7 +410,7 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         // launches need no room
         B.unstored = B.window && c->cfg.max_depth > 0 && depth == c->cfg.max_depth - 1;
         for (u64 a = lo, b = 0; a < hi; a = b) {
-            b = std::min(hi, a + CHUNK);
+            b = std::min(hi, a + chunk);
             if (B.window && !B.unstored) {
                 // [a, count) is live (the rest of the frontier and the level being
                 // built); a state yields at most `bound` new states, so a launch of n
@@ -409,8 +428,21 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                                     std::to_string((c->table_slots * 8) >> 30) + " GiB) so the window gets more");
                 b = a + want;
             }
+            B.vbase = c->h_ctr->count;  // (verification: read back after every launch)
             HIPCHK(c, launch_wexpand(c->WM, B, a, b, c->st));
             c->res.expand_launches += 1;
+            if (B.verify) {
+                // the launch's hits on owners of the same launch, now that they are stored
+                if (int rc = read_counters(c)) return rc;
+                if (c->h_ctr->overflow || c->h_ctr->table_full) break;
+                if (c->h_ctr->vcount > B.vcap)
+                    return fail(c, RMC_E_HIP, "verification: " + std::to_string(b - a) + " states deferred " +
+                                                  std::to_string(c->h_ctr->vcount) + " hits, bound " +
+                                                  std::to_string(vlanes) + " each");
+                HIPCHK(c, launch_wverify(c->WM, B, c->h_ctr->vcount, c->st));
+                HIPCHK(c, hipMemsetAsync(&B.ctr->vcount, 0, 8, c->st));
+                c->h_ctr->vcount = 0;
+            }
             if (B.window) {
                 const u64 before = c->h_ctr->count;
                 if (int rc = read_counters(c)) return rc;
@@ -433,6 +465,10 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         const Counters& k = *c->h_ctr;
         if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full");
         if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, depth));
+        if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full");
+        if (k.overflow & 8u) return fail(c, RMC_E_HIP, "verification: a fingerprint hit has no stored owner");
+        c->res.collisions += k.collisions;
+        c->res.verified += k.vchecked;
         if (k.overflow)
             return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(B.cap) +
                                                " wide states); raise rmc_config.state_capacity");

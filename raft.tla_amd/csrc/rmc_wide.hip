@@ -15,12 +15,15 @@
 namespace rmc {
 namespace wide {
 
-__device__ __forceinline__ int w_insert(u64* __restrict__ table, u64 mask, const Fp& h, u32* full) {
+// 1: h was inserted, 0: it was there (or the table is full).  *at = the slot that
+// holds it (~0: table full) — full-state verification finds the owner by it.
+__device__ __forceinline__ int w_insert(u64* __restrict__ table, u64 mask, const Fp& h, u32* full, u64* at) {
     const TKey t = tkey(h, mask);
     const u64 key = t.v;
     u64 s = t.s0;
     for (u64 n = 0; n <= mask; ++n) {
         const u64 cur = table[s];
+        *at = s;
         if (cur == key) return 0;
         if (cur == 0) {
             const u64 prev = atomicCAS((unsigned long long*)&table[s], 0ull, (unsigned long long)key);
@@ -29,6 +32,7 @@ __device__ __forceinline__ int w_insert(u64* __restrict__ table, u64 mask, const
         }
         s = (s + 1) & mask;
     }
+    *at = ~0ull;
     atomicOr(full, 1u);
     return 0;
 }
@@ -38,6 +42,9 @@ __device__ __forceinline__ u64 w_wave_sum(u64 v) {
     for (int off = 32; off > 0; off >>= 1)
         v += (u64)(u32)__shfl_xor((int)(u32)v, off) | ((u64)(u32)__shfl_xor((int)(u32)(v >> 32), off) << 32);
     return v;
+}
+__device__ __forceinline__ u64 w_bcast(u64 v, int src) {
+    return (u64)(u32)__shfl((int)(u32)v, src) | ((u64)(u32)__shfl((int)(u32)(v >> 32), src) << 32);
 }
 
 // The slot of state i's record: its index, or in the ring window i % window
@@ -70,17 +77,24 @@ __device__ __forceinline__ u32 w_store(const WModel& M, const WideBufs& B, u64 n
 }
 
 // Init (raft.tla:125-129) or SmokeInit's states: n staged records (of the work type).
-template <class Store, class Work, bool Ring>
+// Verify (RMC_FLAG_VERIFY_STATES): the key is weakened as the expansion's and
+// the new state becomes its slot's owner.
+template <class Store, class Work, bool Ring, bool Verify>
 __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B, const Work* staged, u64 n) {
     static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
+    static_assert(!(Ring && Verify), "verification compares with resident records");
     for (u64 t = (u64)blockIdx.x * 256ull + threadIdx.x; t < n; t += (u64)gridDim.x * 256ull) {
-        if (!w_insert(B.table, B.tmask, wfp(staged[t], B.salt, M.S), &B.ctr->table_full)) continue;
+        Fp h = wfp(staged[t], B.salt, M.S);
+        if constexpr (Verify) h = fp_weaken(h, B.fp_mask);
+        u64 slot;
+        if (!w_insert(B.table, B.tmask, h, &B.ctr->table_full, &slot)) continue;
         const u64 ni = atomicAdd((unsigned long long*)&B.ctr->count, 1ull);
         if (ni >= B.cap) {
             atomicOr(&B.ctr->overflow, 1u);
             continue;
         }
         const u32 bad = w_store<Store, Ring>(M, B, ni, staged[t], ~0ull, 255);
+        if constexpr (Verify) B.sidx[slot] = ni;
         if (bad) atomicOr(&B.ctr->overflow, bad << 8);
     }
 }
@@ -96,11 +110,24 @@ __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B,
 // widened into a Work record; lanes, CONSTRAINT and fingerprints run on Work
 // (wfp does not depend on the record's capacity), and a stored successor is
 // narrowed into a Store record (w_store).
-template <class Store, class Work, bool Ring>
+// Verify (RMC_FLAG_VERIFY_STATES, resident store): the inserting lane records
+// itself as its slot's owner (B.sidx: it knows the slot and the index, and the
+// end of the launch publishes the write), and a lane whose key is already in
+// the set compares its private successor with the owner's record — at once
+// when the owner was stored by an earlier launch (index below B.vbase: the
+// record is complete), else through B.vbuf and k_wverify after this launch (the
+// owner's record may be half written: it is never read here).  A successor
+// that differs from its key's owner is a collision: counted and dropped, as
+// TLC would drop it.  The key that reaches the set is weakened by B.fp_mask
+// (rmc_set_fp_bits), and the stutter shortcut — taken on the full fingerprint —
+// is confirmed on the states, so every probe is either a new state or a
+// compared hit: verified = probes - (distinct - 1).
+template <class Store, class Work, bool Ring, bool Verify>
 __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs B, u64 lo, u64 hi) {
     static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
     static_assert(Store::kLW <= Work::kLW && Store::kKW <= Work::kKW, "the work record holds every stored state");
-    u64 gen = 0, probes = 0;
+    static_assert(!(Ring && Verify), "verification compares with resident records");
+    u64 gen = 0, probes = 0, vchk = 0, vcol = 0;
     u32 bad = 0;
     const int o7 = M.L.off[7];
     for (u64 i = lo + (u64)blockIdx.x * 256ull + threadIdx.x; i < hi; i += (u64)gridDim.x * 256ull) {
@@ -122,15 +149,41 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
             }
             if (!win_model(M, t)) continue;
             const Fp h = wfp_delta(s, t, h0, dl, B.salt);
-            if (h.k == h0.k && h.s == h0.s) continue;  // a stutter (or a full-fingerprint twin of the parent)
+            // a stutter (without Verify: or a full-fingerprint twin of the parent)
+            if (h.k == h0.k && h.s == h0.s && (!Verify || wsame(s, t, M.S))) continue;
             ++probes;
-            if (!w_insert(B.table, B.tmask, h, &B.ctr->table_full)) continue;
+            u64 slot;
+            if (!w_insert(B.table, B.tmask, Verify ? fp_weaken(h, B.fp_mask) : h, &B.ctr->table_full, &slot)) {
+                if constexpr (Verify) {
+                    if (slot == ~0ull) continue;  // table full (flagged by the insert)
+                    const u64 ix = B.sidx[slot];
+                    if (ix != ~0ull && ix < B.vbase) {
+                        ++vchk;
+                        vcol += wsame(static_cast<const Store*>(B.store)[ix], t, M.S) ? 0u : 1u;
+                        continue;
+                    }
+                    // the owner is of this launch: deferred, one vcount bump for the lanes here together
+                    const u64 bal = __ballot(1);
+                    const int leader = __ffsll((long long)bal) - 1, me = (int)__lane_id();
+                    u64 q0 = 0;
+                    if (me == leader) q0 = atomicAdd((unsigned long long*)&B.ctr->vcount, (unsigned long long)__popcll(bal));
+                    const u64 q = w_bcast(q0, leader) + (u64)__popcll(bal & ((1ull << me) - 1ull));
+                    if (q < B.vcap) {
+                        B.vbuf[2 * q] = i;
+                        B.vbuf[2 * q + 1] = slot | ((u64)lane << 48);
+                    } else {
+                        atomicOr(&B.ctr->overflow, 4u);
+                    }
+                }
+                continue;
+            }
             const u64 ni = atomicAdd((unsigned long long*)&B.ctr->count, 1ull);
             if (ni >= B.cap) {
                 atomicOr(&B.ctr->overflow, 1u);
                 continue;
             }
             bad |= w_store<Store, Ring>(M, B, ni, t, i, lane);
+            if constexpr (Verify) B.sidx[slot] = ni;
         }
         if (g == 0) atomicMin((unsigned long long*)&B.ctr->deadlock, (unsigned long long)i);
         gen += g;
@@ -140,6 +193,40 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
     if (__lane_id() == 0 && gen) atomicAdd((unsigned long long*)&B.ctr->generated, (unsigned long long)gen);
     if (__lane_id() == 0 && probes) atomicAdd((unsigned long long*)&B.ctr->probes, (unsigned long long)probes);
     if (bad) atomicOr(&B.ctr->overflow, bad << 8);
+    if constexpr (Verify) {
+        vchk = w_wave_sum(vchk);
+        vcol = w_wave_sum(vcol);
+        if (__lane_id() == 0 && vchk) atomicAdd((unsigned long long*)&B.ctr->vchecked, (unsigned long long)vchk);
+        if (__lane_id() == 0 && vcol) atomicAdd((unsigned long long*)&B.ctr->collisions, (unsigned long long)vcol);
+    }
+}
+
+// The deferred hits of the last expansion launch (B.vbuf[0, n)), now that the
+// launch is over and every owner's record and B.sidx entry are written: the
+// successor is re-derived from its parent's record by its lane and compared
+// with the owner's.  A hit without an owner (or a record out of range) is
+// Counters.overflow bit 3, an internal error.
+template <class St>
+__global__ __launch_bounds__(256) void k_wverify(const WModel M, const WideBufs B, u64 n) {
+    u64 vchk = 0, vcol = 0;
+    const St* store = static_cast<const St*>(B.store);
+    for (u64 q = (u64)blockIdx.x * 256ull + threadIdx.x; q < n; q += (u64)gridDim.x * 256ull) {
+        const u64 parent = B.vbuf[2 * q], sl = B.vbuf[2 * q + 1];
+        const u64 slot = sl & ((1ull << 48) - 1ull);
+        const int lane = (int)(sl >> 48);
+        const u64 ix = parent < B.cap && slot <= B.tmask ? B.sidx[slot] : ~0ull;
+        St t;
+        if (ix >= B.cap || wlane(M, store[parent], lane, &t) != W_ON) {
+            atomicOr(&B.ctr->overflow, 8u);
+            continue;
+        }
+        ++vchk;
+        vcol += wsame(store[ix], t, M.S) ? 0u : 1u;
+    }
+    vchk = w_wave_sum(vchk);
+    vcol = w_wave_sum(vcol);
+    if (__lane_id() == 0 && vchk) atomicAdd((unsigned long long*)&B.ctr->vchecked, (unsigned long long)vchk);
+    if (__lane_id() == 0 && vcol) atomicAdd((unsigned long long*)&B.ctr->collisions, (unsigned long long)vcol);
 }
 
 // Every enabled lane of n given states, without dedup (rmc_expand).
@@ -488,25 +575,53 @@ static bool w_dispatch(const WideBufs& B, F f) {
     return false;  // a work record smaller than the store's: no such kernel
 }
 
+// (B.verify: the Verify kernels, which exist for the resident store only)
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st) {
     if (!n) return hipSuccess;
+    if (B.verify && B.window) return hipErrorInvalidValue;
     const bool ok = w_dispatch(B, [&](auto* sp, auto* wp, auto ring) {
         typedef std::remove_pointer_t<decltype(sp)> Store;
         typedef std::remove_pointer_t<decltype(wp)> Work;
-        hipLaunchKernelGGL((k_wseed<Store, Work, decltype(ring)::value>), dim3(grid_for(n, 256, 1024)), dim3(256), 0, st,
-                           M, B, static_cast<const Work*>(staged), n);
+        constexpr bool Ring = decltype(ring)::value;
+        const dim3 grid(grid_for(n, 256, 1024));
+        if constexpr (!Ring) {
+            if (B.verify) {
+                hipLaunchKernelGGL((k_wseed<Store, Work, false, true>), grid, dim3(256), 0, st, M, B,
+                                   static_cast<const Work*>(staged), n);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_wseed<Store, Work, Ring, false>), grid, dim3(256), 0, st, M, B,
+                           static_cast<const Work*>(staged), n);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st) {
     if (hi <= lo) return hipSuccess;
+    if (B.verify && B.window) return hipErrorInvalidValue;
     const bool ok = w_dispatch(B, [&](auto* sp, auto* wp, auto ring) {
         typedef std::remove_pointer_t<decltype(sp)> Store;
         typedef std::remove_pointer_t<decltype(wp)> Work;
-        hipLaunchKernelGGL((k_wexpand<Store, Work, decltype(ring)::value>), dim3(grid_for(hi - lo, 256, 4096)), dim3(256),
-                           0, st, M, B, lo, hi);
+        constexpr bool Ring = decltype(ring)::value;
+        const dim3 grid(grid_for(hi - lo, 256, 4096));
+        if constexpr (!Ring) {
+            if (B.verify) {
+                hipLaunchKernelGGL((k_wexpand<Store, Work, false, true>), grid, dim3(256), 0, st, M, B, lo, hi);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_wexpand<Store, Work, Ring, false>), grid, dim3(256), 0, st, M, B, lo, hi);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t st) {
+    if (!n) return hipSuccess;
+    if (!B.verify || B.window || n > B.vcap) return hipErrorInvalidValue;
+    const dim3 grid(grid_for(n, 256, 4096));
+    if (B.compact == 2) hipLaunchKernelGGL(k_wverify<WStateD>, grid, dim3(256), 0, st, M, B, n);
+    else if (B.compact) hipLaunchKernelGGL(k_wverify<WStateC>, grid, dim3(256), 0, st, M, B, n);
+    else hipLaunchKernelGGL(k_wverify<WState>, grid, dim3(256), 0, st, M, B, n);
+    return hipGetLastError();
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st) {

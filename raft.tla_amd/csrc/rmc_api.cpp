@@ -307,6 +307,83 @@ int read_counters(rmc_ctx* c) {
     return 0;
 }
 
+int seed_done(rmc_ctx* c) {
+    c->res.generated = 1;
+    c->level_start.push_back(0);
+    c->level_start.push_back(c->h_ctr->count);
+    if (c->h_ctr->viol != ~0ull) {
+        c->res.violated_inv = 1 << (int)(c->h_ctr->viol & 15);
+        c->res.violation_depth = 1;
+        c->have_target = 1;
+        c->target_idx = c->h_ctr->viol >> 4;
+    }
+    return c->h_ctr->count ? 1 : 0;
+}
+
+int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
+              std::chrono::steady_clock::time_point t0, const LevelText& text, int* more) {
+    *more = 0;
+    HIPCHK(c, hipEventRecord(c->ev1, c->st));
+    if (int rc = read_counters(c)) return rc;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->res.expand_kernel_seconds += 1e-3 * ms;
+    const Counters& k = *c->h_ctr;
+    if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full");
+    if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, *depth));
+    if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full");
+    if (text.tie_full && (k.overflow & 16u)) return fail(c, RMC_E_CAPACITY, text.tie_full);
+    if (k.overflow & 8u) return fail(c, RMC_E_HIP, text.no_owner);
+    c->res.collisions += k.collisions;
+    c->res.verified += k.vchecked;
+    if (k.overflow)
+        return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(c->B.cap) + " " + text.store_noun +
+                                           "); raise rmc_config.state_capacity");
+    c->res.generated += k.generated;
+    c->res.probes += k.probes;
+    if (text.walked) *text.walked += k.walked;
+    const u64 nnew = k.count - hi;
+    if (nnew) {
+        ++*depth;
+        c->level_start.push_back(k.count);
+    }
+    c->res.distinct = k.count;
+    if (k.viol != ~0ull) {
+        c->res.violated_inv = 1 << (int)(k.viol & 15);
+        c->res.violation_depth = *depth;
+        c->have_target = 1;
+        c->target_idx = k.viol >> 4;
+    } else if ((c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK) && k.deadlock != ~0ull) {
+        c->res.deadlock = 1;
+        c->have_target = 1;
+        c->target_idx = k.deadlock;
+    }
+    if (cb) {
+        rmc_level_stats ls{};
+        ls.level = nnew ? *depth - 1 : *depth;
+        ls.generated = c->res.generated;
+        ls.distinct = k.count;
+        ls.new_states = nnew;
+        ls.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (cb(&ls, user)) {
+            c->res.left_on_queue = nnew;
+            return 0;
+        }
+    }
+    *more = nnew != 0;
+    return 0;
+}
+
+int window_too_small(rmc_ctx* c, u64 win, u64 slot_bytes) {
+    return fail(c, RMC_E_CAPACITY,
+                "spill: the device window (" + std::to_string(win) +
+                    " states) cannot hold the frontier and the level being built; raise "
+                    "rmc_config.device_window, or give the fingerprint set less HBM "
+                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
+                    std::to_string(c->table_slots) + " slots take " +
+                    std::to_string((c->table_slots * slot_bytes) >> 30) + " GiB) so the window gets more");
+}
+
 // ---- frontier spill (RMC_FLAG_SPILL) ---------------------------------------------
 // TLC keeps its state queue in the states/ directory and a trace file of
 // (parent, action) records from which it re-derives counterexample states
@@ -572,82 +649,29 @@ int rmc_create(const rmc_config* cfg, rmc_ctx** out) {
         return 0;
     }
 
-    // ---- capacity: state store + parents + lanes + fingerprint set (load <= 0.5)
-    const u64 per_state = (u64)c->NW * 4 + 8 + 1 + 8 + 1;  // state, parent, lane, footprint, class
-    const bool spill = (cfg->flags & RMC_FLAG_SPILL) != 0;
+    // ---- capacity: state store + parents + lanes + fingerprint set (load <= 0.5):
+    // the division of the budget is rmc_plan.h (host arithmetic, tested without a device)
+    const char* hl = getenv("RMC_SPILL_HOST_LINKS");
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
-    const u64 budget = (u64)((double)fr * 0.80);
-    u64 cap = cfg->state_capacity;
-    // rmc_config.set_bytes (TLC -fpmem): the set's slots, the largest power of two that fits
-    u64 set_slots = set_slots_of(cfg->set_bytes);
-    if (set_slots && cap) {
-        // set_bytes is an upper bound: halved (down to load 1/2) until the store fits
-        // beside it — the states, or spilling the device trace links and the window
-        // the spill sizing below asks for (need_win)
-        const u64 sb = c->sh.verify ? 16 : 8;
-        const u64 need_win = cfg->device_window ? cfg->device_window : cap / (c->sh.verify ? 8 : 4);
-        const u64 store = spill ? cap * 9 + need_win * (per_state - 9) : cap * per_state;
-        while (set_slots > 1024 && set_slots / 2 >= 2 * cap && set_slots * sb + store > budget) set_slots >>= 1;
-    }
-    if (set_slots && cap > set_slots / 2) {
-        c->err = "state_capacity " + std::to_string(cap) + " exceeds what a set of set_bytes " +
-                 std::to_string(cfg->set_bytes) + " holds (" + std::to_string(set_slots / 2) + " states)";
+    PackedPlanIn in{};
+    in.budget = (u64)((double)fr * 0.80);
+    in.state_words = (u64)c->NW;
+    in.state_capacity = cfg->state_capacity;
+    in.set_slots = set_slots_of(cfg->set_bytes);  // rmc_config.set_bytes (TLC -fpmem)
+    in.device_window = cfg->device_window;
+    in.spill = (cfg->flags & RMC_FLAG_SPILL) != 0;
+    in.verify = c->sh.verify;
+    in.host_links = hl && atoi(hl);
+    const PackedPlan plan = packed_plan(in);
+    if (plan.cap_exceeds_set) {
+        c->err = "state_capacity " + std::to_string(cfg->state_capacity) + " exceeds what a set of set_bytes " +
+                 std::to_string(cfg->set_bytes) + " holds (" + std::to_string(plan.set_slots / 2) + " states)";
         return bail(RMC_E_INVAL);
     }
-    if (cap == 0 && set_slots) {
-        // the given set holds set_slots / 2 states; the store fills what the set leaves
-        const u64 fixed = set_slots * (c->sh.verify ? 16 : 8);
-        cap = set_slots / 2;
-        if (!spill) cap = std::min<u64>(cap, (budget - std::min<u64>(budget, fixed)) / per_state);
-    } else if (cap == 0) {
-        // table <= 4 slots per state after pow2 rounding (+ as many sidx words when verifying);
-        // spilling: the largest set of at most half the budget, two slots per state
-        if (spill && c->sh.verify) {  // the set and its slot -> index map: 16 B per slot, <= 2/3 of the budget
-            u64 sl = 1ull << 20;
-            while (sl * 32 <= budget / 3 * 2) sl <<= 1;
-            cap = sl / 2;
-        } else if (spill) {
-            u64 sl = 1ull << 20;
-            while (sl * 16 <= budget / 2) sl <<= 1;  // 8 B * (2 sl) <= budget / 2
-            cap = sl / 2;
-        } else {
-            cap = budget / (per_state + (c->sh.verify ? 64 : 32));
-        }
-        cap = std::min<u64>(cap, 1ull << 36);
-    }
-    cap = std::max<u64>(cap, 1024);
-    u64 slots = 1;
-    while (slots < 2 * cap) slots <<= 1;
-    if (set_slots) slots = std::max(slots, set_slots);
+    const bool spill = in.spill, dev_links = plan.dev_links;
+    const u64 cap = plan.cap, slots = plan.slots, win = plan.window, link_cap = plan.link_cap;
     c->table_slots = slots;
-    u64 win = cap;  // states resident on the device
-    // spilling: the trace links of every state stay on the device (9 B each) when
-    // that leaves a window of at least a quarter of the states; otherwise, or with
-    // RMC_SPILL_HOST_LINKS=1, they move to the host with the spilled levels
-    bool dev_links = false;
-    u64 link_cap = win;
-    if (spill) {
-        // (verification: the slot -> index map and the two hit buffers, 1 GB each)
-        const u64 fixed = slots * (c->sh.verify ? 16 : 8) + (c->sh.verify ? (2ull << 30) : 0);
-        const u64 rest = budget - std::min<u64>(budget, fixed);
-        const char* hl = getenv("RMC_SPILL_HOST_LINKS");
-        const u64 wbytes = per_state - 9;  // state, footprint, class
-        // verification keeps a smaller ring (its set is twice the size): an eighth of the states
-        const u64 need_win = cfg->device_window ? cfg->device_window : cap / (c->sh.verify ? 8 : 4);
-        dev_links = !(hl && atoi(hl)) && rest > cap * 9 && (rest - cap * 9) / wbytes >= need_win;
-        win = cfg->device_window;
-        if (win == 0) win = dev_links ? (rest - cap * 9) / wbytes : rest / per_state;
-        win = std::max<u64>(std::min<u64>(win, cap), 1024);
-        if (dev_links) {
-            // the window is a ring of a power of two states (DevBufs.wmask): a
-            // given window rounds up, librmc's own sizing down
-            u64 p2 = 1024;
-            while (p2 < win) p2 <<= 1;
-            win = (cfg->device_window || p2 == win) ? p2 : p2 >> 1;
-        }
-        link_cap = dev_links ? cap : win;
-    }
     c->B.cap = win;
     c->B.tmask = slots - 1;
     c->B.wmask = dev_links ? win - 1 : ~0ull;
@@ -737,12 +761,8 @@ void rmc_destroy(rmc_ctx* c) {
     delete c;
 }
 
-// The most new states one state's expansion can yield: every lane yields at most
-// one, and the guards of raft.tla's Next (raft.tla:421-430) enable per server i at
-// most Restart + Timeout (a Follower, :136,146), Restart + Timeout + S x RequestVote +
-// BecomeLeader (a Candidate, :157-158,195-196) or Restart + V x ClientRequest +
-// AdvanceCommitIndex + (S - 1) x AppendEntries (a Leader, :171-173,206-207,219-220),
-// plus Receive, Duplicate and Drop per bag slot.  The spill window sizes its
+// The most new states one state's expansion can yield (rmc_plan.h
+// new_states_bound, never more than the lanes).  The spill window sizes its
 // launches by this bound (RMC_LANE_BOUND=0: every lane, the round-5 bound).
 static u64 max_new_per_state(const rmc_ctx* c) {
     const u64 lanes = (u64)c->P.off[10];
@@ -751,30 +771,12 @@ static u64 max_new_per_state(const rmc_ctx* c) {
         return e && atoi(e) == 0;
     }();
     if (all_lanes) return lanes;
-    const u64 S = (u64)c->sh.S, V = (u64)c->P.V, K = (u64)(c->P.off[8] - c->P.off[7]);
-    const u64 per_server = std::max<u64>(std::max<u64>(2, S + 3), S + V + 1);
-    return std::min<u64>(lanes, S * per_server + 3 * K);
+    return packed_new_states_bound(lanes, (u64)c->sh.S, (u64)c->P.V, (u64)(c->P.off[8] - c->P.off[7]));
 }
 
-int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
-    if (!c) return RMC_E_INVAL;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->wide) return run_bfs_wide(c, cb, user);
-    if (c->dist.on) return run_bfs_sharded(c, cb, user);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    const bool resume = c->resume != 0;  // rmc_recover restored store, set and counters
-    c->resume = 0;
-    c->have_target = 0;
-    int depth = 0;
-    if (resume) {
-        c->res.left_on_queue = 0;
-        c->res.seconds = 0;
-        HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
-        c->h_ctr->count = c->level_start.back();
-        if (int rc = reset_counters(c, true)) return rc;
-        depth = c->resume_depth;
-    } else {
+// A fresh run (no rmc_recover before it): clear the result, the set and the
+// counters, and seed Init.  *depth: the level the loop starts from.
+static int start_run(rmc_ctx* c, int* depth) {
     c->res = rmc_result{};
     c->res.set_slots = c->table_slots;
     c->res.spill_links_on_device = c->spill.on && c->spill.dev_links;
@@ -823,19 +825,32 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, launch(c->sh, Op::Seed, c->P, c->PT, c->B, 1, 0, c->d_staged, nullptr, 0, nullptr, c->st));
     if (int rc = read_counters(c)) return rc;
-    c->res.generated = 1;
-    c->level_start.push_back(0);
-    c->level_start.push_back(c->h_ctr->count);
+    *depth = seed_done(c);
     if (c->sh.verify)
         HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, c->h_ctr->count, nullptr, nullptr, 0, nullptr, c->st));
-    depth = c->h_ctr->count ? 1 : 0;
-    if (c->h_ctr->viol != ~0ull) {
-        c->res.violated_inv = 1 << (int)(c->h_ctr->viol & 15);
-        c->res.violation_depth = 1;
-        c->have_target = 1;
-        c->target_idx = c->h_ctr->viol >> 4;
+    return 0;
+}
+
+int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
+    if (!c) return RMC_E_INVAL;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (c->wide) return run_bfs_wide(c, cb, user);
+    if (c->dist.on) return run_bfs_sharded(c, cb, user);
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool resume = c->resume != 0;  // rmc_recover restored store, set and counters
+    c->resume = 0;
+    c->have_target = 0;
+    int depth = 0;
+    if (resume) {
+        c->res.left_on_queue = 0;
+        c->res.seconds = 0;
+        HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+        c->h_ctr->count = c->level_start.back();
+        if (int rc = reset_counters(c, true)) return rc;
+        depth = c->resume_depth;
+    } else if (int rc = start_run(c, &depth)) {
+        return rc;
     }
-    }  // !resume
     // states per expansion launch: at most kMaxLaunch (B.word holds one launch's
     // presorted positions), and a level is cut into EQUAL launches, so no launch
     // is a small remainder that leaves most of the resident grid idle
@@ -845,7 +860,9 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         const int l = e ? std::max(16, std::min(kMaxLaunchLog2, atoi(e))) : kMaxLaunchLog2;
         return 1ull << l;
     }();
-    while (!c->have_target) {
+    const LevelText text = {"verification: a stored state has no fingerprint slot", "symmetry tie buffer full", "states",
+                            &c->walked};
+    for (int more = 1; more && !c->have_target;) {
         const u64 lo = c->level_start[depth - 1], hi = c->level_start[depth];
         if (lo == hi) break;  // fixpoint
         if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
@@ -865,61 +882,39 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         const u64 even = (hi - lo + nlaunch - 1) / nlaunch;  // <= chunk
         for (u64 a = lo, b = 0; a < hi; a = b) {
             b = std::min(hi, a + even);
-            if (c->spill.on && c->spill.dev_links) {
-                // the ring window: [a, count) is live (the rest of the frontier and
-                // the level being built); a state yields at most max_new_per_state
-                // new states, so a launch of n states cannot overwrite a live state
-                // when count + n * that <= a + win — nothing is ever moved
-                const u64 lanes = max_new_per_state(c), count = c->h_ctr->count, win = c->spill.win;
-                const u64 room = count - a < win ? a + win - count : 0;
-                u64 want = std::min(b - a, room / lanes);
-                if (c->sh.verify) want = std::min(want, c->B.hcap / lanes);  // hbuf holds every hit of a launch
-                if (want == 0)
-                    return fail(c, RMC_E_CAPACITY,
-                                "spill: the device window (" + std::to_string(win) +
-                                    " states) cannot hold the frontier and the level being built; raise "
-                                    "rmc_config.device_window, or give the fingerprint set less HBM "
-                                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
-                                    std::to_string(c->table_slots) + " slots take " +
-                                    std::to_string((c->table_slots * (c->sh.verify ? 16 : 8)) >> 30) +
-                                    " GiB) so the window gets more");
-                b = a + want;
-                if (c->sh.verify) {
-                    // the launch may overwrite the ring slots of states below
-                    // count + n * lanes - win (<= a): copy them to the host first, and
-                    // send hits on them to hbuf
-                    const u64 top = count + want * lanes;
-                    const u64 vlo = top > win ? top - win : 0;
-                    if (int rc = verify_copy_out(c, vlo)) return rc;
-                    c->B.vlo = vlo;
-                }
-            } else if (c->spill.on) {
-                // a state yields at most max_new_per_state new states: a launch of
-                // n states stays inside the window when n * that <= room.  Launches
-                // shrink as the window fills; below 2^20 states the expanded
-                // states [base, a) move to the host first — once they are at
-                // least 1/8 of what the move shifts down (or nothing fits)
-                const u64 lanes = max_new_per_state(c);
-                const u64 count = c->h_ctr->count, fit = (c->B.cap - count) / lanes;
+            if (c->spill.on) {
+                // a state yields at most `bound` new states; verification parks
+                // every hit of a launch on a spilled owner in hbuf
+                const u64 bound = max_new_per_state(c), count = c->h_ctr->count;
                 u64 want = b - a;
-                const u64 old = a - c->spill.base;
-                const bool due = fit < std::min<u64>(want, 1ull << 20) && old && (old * 8 >= count - a || fit == 0);
-                if (due)
-                    if (int rc = spill_to(c, a, count)) return rc;
-                want = std::min(want, (c->B.cap - count) / lanes);
-                if (c->sh.verify) {
-                    want = std::min(want, c->B.hcap / lanes);
-                    c->B.vlo = c->spill.base;  // [0, base) were copied to the host by spill_to
+                if (c->sh.verify) want = std::min(want, c->B.hcap / bound);
+                if (c->spill.dev_links) {
+                    // the ring window: nothing is ever moved (rmc_plan.h ring_room)
+                    const u64 win = c->spill.win;
+                    want = std::min(want, ring_room(count, a, win) / bound);
+                    if (c->sh.verify && want) {
+                        // the launch may overwrite the ring slots of states below
+                        // count + n * bound - win (<= a): copy them to the host first, and
+                        // send hits on them to hbuf
+                        const u64 top = count + want * bound;
+                        const u64 vlo = top > win ? top - win : 0;
+                        if (int rc = verify_copy_out(c, vlo)) return rc;
+                        c->B.vlo = vlo;
+                    }
+                } else {
+                    // the linear window: a launch of n states stays inside it when
+                    // n * bound <= its room.  Launches shrink as the window fills;
+                    // below 2^20 states the expanded states [base, a) move to the
+                    // host first — once they are at least 1/8 of what the move
+                    // shifts down (or nothing fits)
+                    const u64 fit = (c->B.cap - count) / bound, old = a - c->spill.base;
+                    const bool due = fit < std::min<u64>(b - a, 1ull << 20) && old && (old * 8 >= count - a || fit == 0);
+                    if (due)
+                        if (int rc = spill_to(c, a, count)) return rc;
+                    want = std::min(want, (c->B.cap - count) / bound);
+                    if (c->sh.verify) c->B.vlo = c->spill.base;  // [0, base) were copied to the host by spill_to
                 }
-                if (want == 0)
-                    return fail(c, RMC_E_CAPACITY,
-                                "spill: the device window (" + std::to_string(c->spill.win) +
-                                    " states) cannot hold the frontier and the level being built; raise "
-                                    "rmc_config.device_window, or give the fingerprint set less HBM "
-                                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
-                                    std::to_string(c->table_slots) + " slots take " +
-                                    std::to_string((c->table_slots * (c->sh.verify ? 16 : 8)) >> 30) +
-                                    " GiB) so the window gets more");
+                if (want == 0) return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
                 b = a + want;
             }
             HIPCHK(c, launch(c->sh, Op::Expand, c->P, c->PT, c->B, a, b, nullptr, nullptr, 0, nullptr, c->st));
@@ -955,55 +950,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 }
             }
         }
-        HIPCHK(c, hipEventRecord(c->ev1, c->st));
-        if (int rc = read_counters(c)) return rc;
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->res.expand_kernel_seconds += 1e-3 * ms;
-        const Counters& k = *c->h_ctr;
-        if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full");
-        if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, depth));
-        if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full");
-        if (k.overflow & 16u) return fail(c, RMC_E_CAPACITY, "symmetry tie buffer full");
-        if (k.overflow & 8u) return fail(c, RMC_E_HIP, "verification: a stored state has no fingerprint slot");
-        c->res.collisions += k.collisions;
-        c->res.verified += k.vchecked;
-        if (k.overflow) {
-            return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(c->B.cap) +
-                                                " states); raise rmc_config.state_capacity");
-        }
-        c->res.generated += k.generated;
-        c->res.probes += k.probes;
-        c->walked += k.walked;
-        const u64 nnew = k.count - hi;
-        if (nnew) {
-            ++depth;
-            c->level_start.push_back(k.count);
-        }
-        c->res.distinct = k.count;
-        if (k.viol != ~0ull) {
-            c->res.violated_inv = 1 << (int)(k.viol & 15);
-            c->res.violation_depth = depth;
-            c->have_target = 1;
-            c->target_idx = k.viol >> 4;
-        } else if ((c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK) && k.deadlock != ~0ull) {
-            c->res.deadlock = 1;
-            c->have_target = 1;
-            c->target_idx = k.deadlock;
-        }
-        if (cb) {
-            rmc_level_stats ls{};
-            ls.level = nnew ? depth - 1 : depth;
-            ls.generated = c->res.generated;
-            ls.distinct = k.count;
-            ls.new_states = nnew;
-            ls.seconds = secs();
-            if (cb(&ls, user)) {
-                c->res.left_on_queue = nnew;
-                break;
-            }
-        }
-        if (!nnew) break;
+        if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
     }
     c->res.distinct = c->level_start.back();
     c->res.depth = depth;
@@ -1011,7 +958,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const double D = (double)c->res.distinct, G = (double)c->res.generated;
     // TLC's "calculated (optimistic)" fingerprint-collision estimate
     c->res.collision_probability = fp_collision_estimate(D, G, c->table_slots, c->set_epoch != 0);
-    c->res.seconds = secs();
+    c->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     // lane efficiency of the walk: enabled lanes / visited slots (the kernels count
     // the slots only when built with -DRMC_WALK_STATS_BUILD: a register in the hot loop)
     if (getenv("RMC_WALK_STATS"))

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -10,6 +11,7 @@
 #include "../../include/rmc.h"
 #include "raft_packed.h"
 #include "rmc_internal.h"
+#include "rmc_plan.h"
 
 // Sharded mode (rmc_shard): this ctx is one rank of a BFS whose fingerprint
 // space is partitioned over `world` GPUs.  The exchange runs
@@ -119,15 +121,6 @@ struct SpillState {
     rmc::u64 host_hits = 0;        // hits checked against host copies in the last run
 };
 
-// rmc_config.set_bytes -> fingerprint-set slots: the largest power of two of
-// 8-B slots within the bytes (at least 1024), 0 when the set is sized automatically
-inline rmc::u64 set_slots_of(rmc::u64 bytes) {
-    if (bytes == 0) return 0;
-    rmc::u64 sl = 1024;
-    while ((sl << 1) * 8 <= bytes) sl <<= 1;
-    return sl;
-}
-
 struct rmc_ctx {
     rmc_config cfg{};
     rmc::Shape sh{};
@@ -190,6 +183,25 @@ void decode_state(const rmc_ctx* c, const rmc::u32* in, rmc_state_view* v);
 void init_view(const rmc_config& g, rmc_state_view* v);
 int reset_counters(rmc_ctx* c, bool keep_count);
 int read_counters(rmc_ctx* c);
+// After the seed launch's read_counters, on either layout: level 1 is the states
+// it stored, and an invariant Init violates is the target.  Returns the depth.
+int seed_done(rmc_ctx* c);
+// What the level epilogue of the two layouts differs in.
+struct LevelText {
+    const char* no_owner;    // RMC_E_HIP message of Counters.overflow & 8
+    const char* tie_full;    // RMC_E_CAPACITY message of Counters.overflow & 16 (nullptr: no tie buffer)
+    const char* store_noun;  // "state store full (capacity N <noun>)"
+    rmc::u64* walked;        // accumulates Counters.walked (nullptr: not counted)
+};
+// The end of a level's launches (hi: the states before it), from the closing
+// event to the progress callback: kernel time, the Counters.overflow errors,
+// the result's totals, level_start / depth, the violation or deadlock target.
+// *more = 0 when the search ends here: no new states, or the callback stopped it.
+int end_level(rmc_ctx* c, rmc::u64 hi, int* depth, rmc_progress_fn cb, void* user,
+              std::chrono::steady_clock::time_point t0, const LevelText& text, int* more);
+// RMC_E_CAPACITY: a spilled search whose window of `win` states has no room for
+// one more launch (ring_room, rmc_plan.h) beside a set of slot_bytes per slot
+int window_too_small(rmc_ctx* c, rmc::u64 win, rmc::u64 slot_bytes);
 // RMC_E_CAPACITY message for an unbounded field a successor took past the
 // packed capacity (Counters.overflow bits 8-11), "" if none
 std::string capacity_message(const rmc_ctx* c, rmc::u32 overflow, int depth);

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rmc_ctx.h"
@@ -99,23 +100,26 @@ static int wide_work(const rmc_config& g, int store) {
     if (const char* e = getenv("RMC_WIDE_WORK")) w = std::max(0, std::min(2, atoi(e)));
     return std::min(w, store);  // (0 is the largest record)
 }
+// Calls f with a null pointer to the record of a kind (WideBufs.compact / .work),
+// the idiom of rmc_wide.hip's w_dispatch.
+template <class F>
+static auto with_record(int kind, F f) {
+    return kind == 2 ? f((WStateD*)nullptr) : kind == 1 ? f((WStateC*)nullptr) : f((WState*)nullptr);
+}
 static size_t record_bytes(int kind) {
-    return kind == 2 ? sizeof(WStateD) : kind == 1 ? sizeof(WStateC) : sizeof(WState);
+    return with_record(kind, [](auto* r) { return sizeof *r; });
 }
 size_t wide_record_bytes(const rmc_config& g) { return record_bytes(wide_compact(g)); }
 
-// The most new states one state's expansion can yield (rmc_api.cpp
-// max_new_per_state, the guards of raft.tla's Next) with the wide bag: per
-// server Restart + Timeout, or + S x RequestVote + BecomeLeader, or Restart +
-// V x ClientRequest + AdvanceCommitIndex + (S - 1) x AppendEntries, plus Receive,
+// The most new states one state's expansion can yield (rmc_plan.h
+// new_states_bound, the guards of raft.tla's Next) with the wide bag: Receive,
 // Duplicate and Drop per message of a bag in the model and in the work record.
 static u64 wide_bag(const rmc_config& g, int work) {  // messages of a stored state at most
     const u64 kw = work == 2 ? KWD : work == 1 ? KWC : KW;
     return std::min<u64>((u64)g.max_msgs, kw);
 }
 static u64 wide_new_per_state(const rmc_config& g, int work) {
-    const u64 S = (u64)g.n_servers, V = (u64)g.n_values;
-    return S * std::max<u64>(std::max<u64>(2, S + 3), S + V + 1) + 3 * wide_bag(g, work);
+    return new_states_bound((u64)g.n_servers, (u64)g.n_values, wide_bag(g, work));
 }
 
 // ---- codec ----------------------------------------------------------------------
@@ -348,7 +352,6 @@ static u64 wide_salt(u64 seed) { return seed ? (mix64(seed) & ((1ull << 59) - 1)
 // ---- BFS (TLC's worker loop on the wide layout) ----------------------------------------
 int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const auto t0 = std::chrono::steady_clock::now();
-    auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     if (c->resume) return fail(c, RMC_E_STATE, "recover: not supported on the wide layout");
     WideBufs B = c->WB;
     B.salt = wide_salt(c->cfg.seed);
@@ -366,29 +369,15 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->h_ctr->count = 0;
     if (int rc = reset_counters(c, false)) return rc;
     // Init in the record the seed kernel reads: the work record (= the store's without the ring)
-    const int seed_rec = B.window ? B.work : B.compact;
-    WState init;
-    WStateC initc;
-    WStateD initd;
-    winit(c->WM, init);
-    winit(c->WM, initc);
-    winit(c->WM, initd);
-    if (seed_rec == 2) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initd, sizeof initd, hipMemcpyHostToDevice, c->st));
-    else if (seed_rec) HIPCHK(c, hipMemcpyAsync(c->w_staged, &initc, sizeof initc, hipMemcpyHostToDevice, c->st));
-    else HIPCHK(c, hipMemcpyAsync(c->w_staged, &init, sizeof init, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging copies live on this stack frame)
+    HIPCHK(c, with_record(B.window ? B.work : B.compact, [&](auto* r) {
+        std::remove_pointer_t<decltype(r)> init;
+        winit(c->WM, init);
+        const hipError_t e = hipMemcpyAsync(c->w_staged, &init, sizeof init, hipMemcpyHostToDevice, c->st);
+        return e != hipSuccess ? e : hipStreamSynchronize(c->st);  // (init lives on this stack frame)
+    }));
     HIPCHK(c, launch_wseed(c->WM, B, c->w_staged, 1, c->st));
     if (int rc = read_counters(c)) return rc;
-    c->res.generated = 1;
-    c->level_start.push_back(0);
-    c->level_start.push_back(c->h_ctr->count);
-    int depth = c->h_ctr->count ? 1 : 0;
-    if (c->h_ctr->viol != ~0ull) {
-        c->res.violated_inv = 1 << (int)(c->h_ctr->viol & 15);
-        c->res.violation_depth = 1;
-        c->have_target = 1;
-        c->target_idx = c->h_ctr->viol >> 4;
-    }
+    int depth = seed_done(c);
     const u64 CHUNK = 1ull << 22;
     const u64 bound = wide_new_per_state(c->cfg, B.work);
     u64 records = c->h_ctr->count;  // ring: records written so far
@@ -397,7 +386,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     // work record — so one of at most vcap / lanes states cannot overflow vbuf
     const u64 vlanes = (u64)c->WM.L.off[7] + 3 * wide_bag(c->cfg, B.work);
     const u64 chunk = B.verify ? std::max<u64>(1, std::min(CHUNK, B.vcap / vlanes)) : CHUNK;
-    while (!c->have_target) {
+    const LevelText text = {"verification: a fingerprint hit has no stored owner", nullptr, "wide states", nullptr};
+    for (int more = 1; more && !c->have_target;) {
         const u64 lo = c->level_start[(size_t)depth - 1], hi = c->level_start[(size_t)depth];
         if (lo == hi) break;
         if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
@@ -412,20 +402,9 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         for (u64 a = lo, b = 0; a < hi; a = b) {
             b = std::min(hi, a + chunk);
             if (B.window && !B.unstored) {
-                // [a, count) is live (the rest of the frontier and the level being
-                // built); a state yields at most `bound` new states, so a launch of n
-                // states overwrites no live record when count + n * bound <= a + window
-                const u64 count = c->h_ctr->count, win = B.window;
-                const u64 room = count - a < win ? a + win - count : 0;
-                const u64 want = std::min(b - a, room / bound);
-                if (want == 0)
-                    return fail(c, RMC_E_CAPACITY,
-                                "spill: the device window (" + std::to_string(win) +
-                                    " states) cannot hold the frontier and the level being built; raise "
-                                    "rmc_config.device_window, or give the fingerprint set less HBM "
-                                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
-                                    std::to_string(c->table_slots) + " slots take " +
-                                    std::to_string((c->table_slots * 8) >> 30) + " GiB) so the window gets more");
+                // a launch overwrites no live record (rmc_plan.h ring_room)
+                const u64 want = std::min(b - a, ring_room(c->h_ctr->count, a, B.window) / bound);
+                if (want == 0) return window_too_small(c, B.window, 8);
                 b = a + want;
             }
             B.vbase = c->h_ctr->count;  // (verification: read back after every launch)
@@ -457,59 +436,14 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 c->res.spills = records / B.window;  // passes of the ring
             }
         }
-        HIPCHK(c, hipEventRecord(c->ev1, c->st));
-        if (int rc = read_counters(c)) return rc;
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->res.expand_kernel_seconds += 1e-3 * ms;
-        const Counters& k = *c->h_ctr;
-        if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full");
-        if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, depth));
-        if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full");
-        if (k.overflow & 8u) return fail(c, RMC_E_HIP, "verification: a fingerprint hit has no stored owner");
-        c->res.collisions += k.collisions;
-        c->res.verified += k.vchecked;
-        if (k.overflow)
-            return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(B.cap) +
-                                               " wide states); raise rmc_config.state_capacity");
-        c->res.generated += k.generated;
-        c->res.probes += k.probes;
-        const u64 nnew = k.count - hi;
-        if (nnew) {
-            ++depth;
-            c->level_start.push_back(k.count);
-        }
-        c->res.distinct = k.count;
-        if (k.viol != ~0ull) {
-            c->res.violated_inv = 1 << (int)(k.viol & 15);
-            c->res.violation_depth = depth;
-            c->have_target = 1;
-            c->target_idx = k.viol >> 4;
-        } else if ((c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK) && k.deadlock != ~0ull) {
-            c->res.deadlock = 1;
-            c->have_target = 1;
-            c->target_idx = k.deadlock;
-        }
-        if (cb) {
-            rmc_level_stats ls{};
-            ls.level = nnew ? depth - 1 : depth;
-            ls.generated = c->res.generated;
-            ls.distinct = k.count;
-            ls.new_states = nnew;
-            ls.seconds = secs();
-            if (cb(&ls, user)) {
-                c->res.left_on_queue = nnew;
-                break;
-            }
-        }
-        if (!nnew) break;
+        if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
     }
     c->res.distinct = c->level_start.back();
     c->res.depth = depth;
     c->res.stored_here = c->res.distinct;
     const double Dd = (double)c->res.distinct, G = (double)c->res.generated;
     c->res.collision_probability = fp_collision_estimate(Dd, G, (c->WB.tmask + 1));
-    c->res.seconds = secs();
+    c->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
@@ -550,19 +484,13 @@ int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* i
         return 0;
     }
     for (size_t q = 0; q < chain.size() && q < cap; ++q) {
-        if (c->WB.compact == 2) {
-            WStateD s;
-            HIPCHK(c, hipMemcpy(&s, static_cast<const WStateD*>(c->WB.store) + chain[q], sizeof s, hipMemcpyDeviceToHost));
-            if (states) decode_wide(c, s, &states[q]);
-        } else if (c->WB.compact) {
-            WStateC s;
-            HIPCHK(c, hipMemcpy(&s, static_cast<const WStateC*>(c->WB.store) + chain[q], sizeof s, hipMemcpyDeviceToHost));
-            if (states) decode_wide(c, s, &states[q]);
-        } else {
-            WState s;
-            HIPCHK(c, hipMemcpy(&s, static_cast<const WState*>(c->WB.store) + chain[q], sizeof s, hipMemcpyDeviceToHost));
-            if (states) decode_wide(c, s, &states[q]);
-        }
+        HIPCHK(c, with_record(c->WB.compact, [&](auto* r) {
+            std::remove_pointer_t<decltype(r)> s;
+            const hipError_t e =
+                hipMemcpy(&s, static_cast<decltype(r)>(c->WB.store) + chain[q], sizeof s, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && states) decode_wide(c, s, &states[q]);
+            return e;
+        }));
         if (families) families[q] = wide_family(c, acts[q]);
         if (instances) instances[q] = acts[q] == 255 ? -1 : acts[q];
     }

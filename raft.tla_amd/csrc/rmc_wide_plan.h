@@ -6,6 +6,8 @@
 
 #include <algorithm>
 
+#include "rmc_plan.h"  // set_slots_of: WidePlanIn.set_slots from rmc_config.set_bytes
+
 namespace rmc_host {
 
 struct WidePlanIn {

@@ -18,6 +18,7 @@
 
 #include "raft_packed.h"
 #include "rmc_internal.h"
+#include "rmc_units.h"
 
 namespace rmc {
 
@@ -755,6 +756,7 @@ struct ExpandDefaults {
     static constexpr bool REP = false;      // a replicated level (B.rep)
     static constexpr bool PRESORT = false;  // windows sorted before the launch (k_window_order, B.word)
     static constexpr int DYN = 0;           // dynamic per-wave work units
+    static constexpr int UNIT_TILES = 16;   // DYN: tiles per unit (rmc_units.h; 16: a wave's quarter of a whole window)
     static constexpr bool POOL = false;     // the pool flush
 };
 
@@ -773,7 +775,7 @@ template <int S, int K, class C>
 __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi) {
     constexpr bool SYM = C::SYM, DIST = C::DIST, VERIFY = C::VERIFY, PRE = C::PRE, SORT = C::SORT, DIA = C::DIA,
                    REP = C::REP, PRESORT = C::PRESORT, POOL = C::POOL;
-    constexpr int BATCH = C::BATCH, WTILES = C::WTILES, PIPE = C::PIPE, DYN = C::DYN;
+    constexpr int BATCH = C::BATCH, WTILES = C::WTILES, PIPE = C::PIPE, DYN = C::DYN, UT = C::UNIT_TILES;
     constexpr bool MARK = POOL || REP;  // send markers in the local set
     static_assert(!MARK || (DIST && !VERIFY && !SYM), "send markers: the plain sharded kernel only");
     static_assert(!POOL || !REP, "the pool flush: not on a replicated level");
@@ -790,10 +792,13 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
     static_assert(!PRESORT || (SORT && !REP), "presorted windows: the sorted kernels");
     constexpr bool INSORT = SORT && !PRESORT;
     // DYN: each wave takes its next unit of work — one wave's quarter of a
-    // presorted window (its 64 lanes of every tile) — from a launch-wide
-    // counter, instead of the block's fixed share of windows: the waves end
-    // together however unequal the units' costs and whatever the window count
+    // tile group of a presorted window (its 64 lanes of UT tiles; rmc_units.h)
+    // — from a launch-wide counter, instead of the block's fixed share of
+    // windows: the waves end together however unequal the units' costs and
+    // whatever the window count, and the launch drains over one unit's time,
+    // which is why the unit is shorter than a window
     static_assert(DYN == 0 || PRESORT, "dynamic units: presorted windows");
+    static_assert(UT >= 1 && UT <= 16 && (UT & (UT - 1)) == 0, "unit tiles: a power of two, at most 16");
     // (the marker kernel measured no gain from PIPE at one rank: 308.7-309.7 vs 307.4-308.7 ms)
     constexpr int NW = 2 * S + K;
     typedef RepRec<S, K> RR;
@@ -842,18 +847,39 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
         wt = per_block < (u64)WT ? (per_block ? per_block : 1ull) : (u64)WT;
     }
     u32 q64 = (u32)threadIdx.x & ~63u;  // this thread's window slot base (DYN: the unit's)
+    constexpr bool GROUPS = DYN != 0 && UT < WT;  // units of part of a window's tiles
+    // GROUPS: the unit's first tile as a quarter tile of the window (tile * 4 +
+    // quarter, a step of 4 per tile: the quarter rides in the loop counter, not
+    // in q64) and the tile after its last; the walk's bound is wn cut to that
+    // tile, so the unit adds no scalar held over the walk
+    int wk0 = 0;
+    u32 tile1 = 0;
     u64 win = DYN ? 0ull : (u64)blockIdx.x * 256ull * wt;
     for (;; win += (u64)gridDim.x * 256ull * wt) {  // block-uniform (DYN: wave-uniform)
     if constexpr (DYN != 0) {
         u32 unit = 0;
         if (me == 0) unit = (u32)atomicAdd((unsigned long long*)&B.ctr->wnext, 1ull);
-        unit = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)unit, 0));
-        win = (u64)(unit >> 2) * 256ull * wt;
-        q64 = (unit & 3u) * 64u;
+        if constexpr (GROUPS) {
+            // decoded by lane 0 before the broadcast: the division's temporaries are
+            // vector registers, free between two units, not scalars held over the walk
+            const rmc_units::Unit un =
+                rmc_units::unit_decode(unit, (u32)wt, (u32)UT, rmc_units::unit_groups((u32)wt, (u32)UT));
+            win = bcast64(un.win, 0);
+            const u32 pk = (u32)__builtin_amdgcn_readlane(
+                (int)(un.quarter | (un.tile0 << 2) | ((un.tile0 + un.ntiles) << 8)), 0);
+            wk0 = (int)(pk & 255u);
+            tile1 = pk >> 8;
+        } else {
+            unit = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)unit, 0));
+            const rmc_units::Unit un = rmc_units::unit_decode(unit, (u32)wt, (u32)UT, 1u);
+            win = un.win;
+            q64 = un.quarter * 64u;
+        }
     }
     if (win >= nf) break;
     u32 wn = 0;  // SORT: states in this window
     if constexpr (SORT) wn = (u32)((nf - win) < 256ull * wt ? (nf - win) : 256ull * wt);
+    if constexpr (GROUPS) wn = wn < tile1 * 256u ? wn : tile1 * 256u;  // ... up to the unit's last tile
     if constexpr (INSORT) {
         __syncthreads();  // the previous window's s_ord is consumed
         if (threadIdx.x < NBIN) s_wbin[threadIdx.x] = 0;
@@ -891,11 +917,11 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
         }
         __syncthreads();
     }
-    for (int wk = 0; wk < (int)wt; ++wk) {
+    for (int wk = GROUPS ? wk0 : 0; GROUPS ? ((u32)wk & ~3u) * 64u < wn : wk < (int)wt; wk += GROUPS ? 4 : 1) {
         u64 rel;
         bool live;
         if constexpr (SORT) {
-            const u32 p = (u32)wk * 256u + q64 + (u32)me;
+            const u32 p = GROUPS ? (u32)wk * 64u + (u32)me : (u32)wk * 256u + q64 + (u32)me;
             live = p < wn;
             if constexpr (PRESORT) rel = win + (live ? (u32)B.word[win + p] : 0u);
             else rel = win + (live ? s_ord[p] : 0u);
@@ -1275,6 +1301,12 @@ template <int BATCH_, int PI>
 struct ExpandSort : ExpandDefaults {
     static constexpr bool SORT = true, PRESORT = true, DIA = true;
     static constexpr int BATCH = BATCH_, WTILES = 16, PIPE = PI, DYN = 1;
+    // tiles per unit: 8 measured best of 16, 8, 4, 2 on MCraftBenchXL (profiles/r09/units/);
+    // -DRMC_UNIT_TILES=... builds the other rungs of the ladder for an A/B
+#ifndef RMC_UNIT_TILES
+#define RMC_UNIT_TILES 8
+#endif
+    static constexpr int UNIT_TILES = RMC_UNIT_TILES;
 };
 template <int S, int K, int BATCH, int PI, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_expand_sort(

@@ -1,20 +1,14 @@
 // rmc_api.cpp — the C ABI of librmc.so (include/rmc.h): context, BFS driver,
-// codec, traces, and the differential-test entry point.
+// traces, simulation, and the differential-test entry point.  (The codecs are
+// rmc_codec.cpp, the frontier spill rmc_spill.cpp, checkpoints rmc_ckpt.cpp.)
 //
 // Host side of the hot path: one HIP stream per context, one kernel launch
 // (plus one 40-byte counter read-back) per BFS level.  The level loop
 // replaces TLC's ModelChecker.runTLC / Worker loop.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstddef>
 #include <cstdio>
 #include <cstring>
-#include <random>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <sys/mman.h>
@@ -23,9 +17,7 @@
 
 using namespace rmc;
 
-namespace {
-const char* kVersion = "rmc 2 (raft.tla BFS, gfx950 HIP, packed-delta lanes, HBM fp set, RCCL sharding)";
-}  // namespace
+static const char* kVersion = "rmc 2 (raft.tla BFS, gfx950 HIP, packed-delta lanes, HBM fp set, RCCL sharding)";
 
 namespace rmc_host {
 
@@ -96,180 +88,6 @@ void fill_params(rmc_ctx* c) {
     }
 }
 
-int family_of(const Params& P, int lane) {
-    if (lane == 255) return -1;
-    for (int f = 0; f < 10; ++f)
-        if (lane < P.off[f + 1]) return f;
-    return -1;
-}
-
-// ---- codec ----------------------------------------------------------------------
-int encode_view(const rmc_ctx* c, const rmc_state_view& v, u32* out, std::string* why) {
-    const int S = c->sh.S, K = c->sh.K;
-    const int VR = VR_SH, VG = VR_SH + S, NI = VR_SH + 2 * S, MI = VR_SH + 4 * S;
-    auto bad = [&](const std::string& s) { *why = s; return RMC_E_INVAL; };
-    if (v.n_servers != S) return bad("view n_servers differs from config");
-    if (v.n_msgs < 0 || v.n_msgs > K) return bad("too many messages for the packed bag");
-    for (int i = 0; i < S; ++i) {
-        const int len = v.log_len[i];
-        if (v.currentTerm[i] < 0 || v.currentTerm[i] > 15) return bad("currentTerm out of packed range");
-        if (v.state[i] < 0 || v.state[i] > 2) return bad("state out of range");
-        if (v.votedFor[i] < -1 || v.votedFor[i] >= S) return bad("votedFor out of range");
-        if (v.commitIndex[i] < 0 || v.commitIndex[i] > 3) return bad("commitIndex out of packed range");
-        if (len < 0 || len > LOG_CAP) return bad("log length out of packed range");
-        u64 w = (u64)v.currentTerm[i] | ((u64)v.state[i] << ST_SH) |
-                ((u64)(v.votedFor[i] < 0 ? NILV : (u32)v.votedFor[i]) << VF_SH) | ((u64)v.commitIndex[i] << CI_SH) |
-                ((u64)len << LEN_SH);
-        for (int x = 0; x < len; ++x) {
-            const rmc_entry e = v.log[i][x];
-            if (e.term < 0 || e.term > 15 || e.value < 0 || e.value > 1) return bad("log entry out of range");
-            w |= (u64)(e.term | (e.value << 4)) << (LOG_SH + ENT_W * x);
-        }
-        if ((v.votesResponded[i] | v.votesGranted[i]) >> S) return bad("vote set out of range");
-        w |= (u64)v.votesResponded[i] << VR;
-        w |= (u64)v.votesGranted[i] << VG;
-        for (int j = 0; j < S; ++j) {
-            if (v.nextIndex[i][j] < 1 || v.nextIndex[i][j] > 4) return bad("nextIndex out of packed range");
-            if (v.matchIndex[i][j] < 0 || v.matchIndex[i][j] > 3) return bad("matchIndex out of packed range");
-            w |= (u64)(v.nextIndex[i][j] - 1) << (NI + 2 * j);
-            w |= (u64)v.matchIndex[i][j] << (MI + 2 * j);
-        }
-        out[2 * i] = (u32)w;
-        out[2 * i + 1] = (u32)(w >> 32);
-    }
-    std::vector<u32> slots;
-    for (int q = 0; q < v.n_msgs; ++q) {
-        const rmc_msg_view& m = v.msgs[q];
-        if (m.mtype < 0 || m.mtype > 3) return bad("mtype out of range");
-        if (m.msource < 0 || m.msource >= S || m.mdest < 0 || m.mdest >= S) return bad("message endpoint out of range");
-        if (m.mterm < 0 || m.mterm > 15) return bad("mterm out of packed range");
-        if (m.count < 1 || m.count > 3) return bad("message count out of packed range");
-        u32 s = m_hdr((u32)m.mtype, (u32)m.msource, (u32)m.mdest, (u32)m.mterm);
-        switch (m.mtype) {
-            case RVQ:
-                if (m.mlastLogTerm < 0 || m.mlastLogTerm > 15 || m.mlastLogIndex < 0 || m.mlastLogIndex > 3)
-                    return bad("RequestVoteRequest field out of packed range");
-                s |= ((u32)m.mlastLogTerm << 12) | ((u32)m.mlastLogIndex << 16);
-                break;
-            case RVP: {
-                if (m.mlog_len < 0 || m.mlog_len > 3) return bad("mlog too long");
-                u32 lg = (u32)m.mlog_len;
-                for (int x = 0; x < m.mlog_len; ++x) {
-                    if (m.mlog[x].term < 0 || m.mlog[x].term > 15 || m.mlog[x].value < 0 || m.mlog[x].value > 1)
-                        return bad("mlog entry out of range");
-                    lg |= (u32)(m.mlog[x].term | (m.mlog[x].value << 4)) << (2 + ENT_W * x);
-                }
-                s |= ((u32)(m.mvoteGranted != 0) << 12) | (lg << 13);
-                break;
-            }
-            case AEQ: {
-                if (m.mprevLogIndex < -1 || m.mprevLogIndex > 3 || m.mprevLogTerm < 0 || m.mprevLogTerm > 15 ||
-                    m.mentries_len < 0 || m.mentries_len > 1 || m.mcommitIndex < 0 || m.mcommitIndex > 3)
-                    return bad("AppendEntriesRequest field out of packed range");
-                u32 e = 0;
-                if (m.mentries_len) {
-                    if (m.mentries[0].term < 0 || m.mentries[0].term > 15 || m.mentries[0].value < 0 ||
-                        m.mentries[0].value > 1)
-                        return bad("mentries entry out of range");
-                    e = (u32)(m.mentries[0].term | (m.mentries[0].value << 4));
-                }
-                s |= ((u32)(m.mprevLogIndex + 1) << 12) | ((u32)m.mprevLogTerm << 15) |
-                     ((u32)m.mentries_len << 19) | (e << 20) | ((u32)m.mcommitIndex << 25);
-                break;
-            }
-            default:
-                if (m.mmatchIndex < 0 || m.mmatchIndex > 3) return bad("mmatchIndex out of packed range");
-                s |= ((u32)(m.msuccess != 0) << 12) | ((u32)m.mmatchIndex << 13);
-        }
-        for (u32 o : slots)
-            if ((o & MSG_MASK) == s) return bad("duplicate message in bag view");
-        slots.push_back(s | ((u32)m.count << 30));
-    }
-    std::sort(slots.begin(), slots.end(), [](u32 a, u32 b) { return a > b; });
-    for (int q = 0; q < K; ++q) out[2 * S + q] = q < (int)slots.size() ? slots[q] : 0u;
-    return 0;
-}
-
-void decode_state(const rmc_ctx* c, const u32* in, rmc_state_view* v) {
-    const int S = c->sh.S, K = c->sh.K;
-    const int VR = VR_SH, VG = VR_SH + S, NI = VR_SH + 2 * S, MI = VR_SH + 4 * S;
-    memset(v, 0, sizeof *v);
-    v->n_servers = S;
-    for (int i = 0; i < S; ++i) {
-        const u64 w = (u64)in[2 * i] | ((u64)in[2 * i + 1] << 32);
-        v->currentTerm[i] = (int)w_ct(w);
-        v->state[i] = (int)w_st(w);
-        v->votedFor[i] = w_vf(w) == NILV ? -1 : (int)w_vf(w);
-        v->commitIndex[i] = (int)w_ci(w);
-        v->log_len[i] = (int)w_len(w);
-        for (u32 x = 0; x < w_len(w); ++x) {
-            v->log[i][x].term = (int)(w_ent(w, x) & 15u);
-            v->log[i][x].value = (int)(w_ent(w, x) >> 4);
-        }
-        v->votesResponded[i] = bits(w, VR, S);
-        v->votesGranted[i] = bits(w, VG, S);
-        for (int j = 0; j < S; ++j) {
-            v->nextIndex[i][j] = (int)bits(w, NI + 2 * j, 2) + 1;
-            v->matchIndex[i][j] = (int)bits(w, MI + 2 * j, 2);
-        }
-    }
-    int n = 0;
-    for (int q = 0; q < K; ++q) {
-        const u32 s = in[2 * S + q];
-        if (!s) continue;
-        rmc_msg_view& m = v->msgs[n++];
-        m.mtype = (int)m_type(s);
-        m.msource = (int)m_src(s);
-        m.mdest = (int)m_dst(s);
-        m.mterm = (int)m_term(s);
-        m.count = (int)m_cnt(s);
-        switch (m.mtype) {
-            case RVQ:
-                m.mlastLogTerm = (int)((s >> 12) & 15u);
-                m.mlastLogIndex = (int)((s >> 16) & 3u);
-                break;
-            case RVP: {
-                m.mvoteGranted = (int)((s >> 12) & 1u);
-                const u32 lg = (s >> 13) & 0x1FFFFu;
-                m.mlog_len = (int)(lg & 3u);
-                for (int x = 0; x < m.mlog_len; ++x) {
-                    const u32 e = (lg >> (2 + ENT_W * x)) & 31u;
-                    m.mlog[x].term = (int)(e & 15u);
-                    m.mlog[x].value = (int)(e >> 4);
-                }
-                break;
-            }
-            case AEQ: {
-                m.mprevLogIndex = (int)((s >> 12) & 7u) - 1;
-                m.mprevLogTerm = (int)((s >> 15) & 15u);
-                m.mentries_len = (int)((s >> 19) & 1u);
-                const u32 e = (s >> 20) & 31u;
-                if (m.mentries_len) {
-                    m.mentries[0].term = (int)(e & 15u);
-                    m.mentries[0].value = (int)(e >> 4);
-                }
-                m.mcommitIndex = (int)((s >> 25) & 3u);
-                break;
-            }
-            default:
-                m.msuccess = (int)((s >> 12) & 1u);
-                m.mmatchIndex = (int)((s >> 13) & 3u);
-        }
-    }
-    v->n_msgs = n;
-}
-
-void init_view(const rmc_config& g, rmc_state_view* v) {  // Init raft.tla:113-129
-    memset(v, 0, sizeof *v);
-    v->n_servers = g.n_servers;
-    for (int i = 0; i < g.n_servers; ++i) {
-        v->currentTerm[i] = 1;
-        v->state[i] = 0;
-        v->votedFor[i] = -1;
-        for (int j = 0; j < g.n_servers; ++j) v->nextIndex[i][j] = 1;
-    }
-}
-
 int reset_counters(rmc_ctx* c, bool keep_count) {
     Counters h{};
     h.count = keep_count ? c->h_ctr->count : 0;
@@ -278,13 +96,6 @@ int reset_counters(rmc_ctx* c, bool keep_count) {
     *c->h_ctr = h;
     HIPCHK(c, hipMemcpyAsync(c->B.ctr, c->h_ctr, sizeof(Counters), hipMemcpyHostToDevice, c->st));
     return 0;
-}
-
-// The checkpoint file of this ctx's part: <path> on one GPU, <path>.rank<r>
-// for rank r of a sharded search.
-std::string shard_path(const rmc_ctx* c, const char* path) {
-    if (!c->dist.on || c->dist.world <= 1) return path;
-    return std::string(path) + ".rank" + std::to_string(c->dist.rank);
 }
 
 std::string capacity_message(const rmc_ctx* c, u32 overflow, int depth) {
@@ -371,221 +182,6 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
         }
     }
     *more = nnew != 0;
-    return 0;
-}
-
-int window_too_small(rmc_ctx* c, u64 win, u64 slot_bytes) {
-    return fail(c, RMC_E_CAPACITY,
-                "spill: the device window (" + std::to_string(win) +
-                    " states) cannot hold the frontier and the level being built; raise "
-                    "rmc_config.device_window, or give the fingerprint set less HBM "
-                    "(rmc_config.set_bytes, rmc-tlc -fpmem: its " +
-                    std::to_string(c->table_slots) + " slots take " +
-                    std::to_string((c->table_slots * slot_bytes) >> 30) + " GiB) so the window gets more");
-}
-
-// ---- frontier spill (RMC_FLAG_SPILL) ---------------------------------------------
-// TLC keeps its state queue in the states/ directory and a trace file of
-// (parent, action) records from which it re-derives counterexample states
-// (SURVEY.md §8f rank 4).  Here the fingerprint set and the state window stay
-// in HBM; spilled states keep only their trace links in host memory.  Kernels
-// index states by their global index through device pointers biased by -base.
-void spill_rebase(rmc_ctx* c, u64 base) {
-    SpillState& X = c->spill;
-    X.base = base;
-    if (X.dev_links) {  // the ring window (DevBufs.wmask): nothing moves, base = the oldest resident state
-        c->B.store = X.store;
-        c->B.parent = X.parent;
-        c->B.act = X.act;
-        c->B.foot = X.foot;
-        c->B.cls = X.cls;
-        c->B.cap = X.total_cap;
-        return;
-    }
-    const uintptr_t nw = (uintptr_t)c->NW;
-    c->B.store = (u32*)((uintptr_t)X.store - (uintptr_t)base * nw * 4);
-    const u64 lb = X.dev_links ? 0 : base;  // device links: indexed by global index, never rebased
-    c->B.parent = (u64*)((uintptr_t)X.parent - (uintptr_t)lb * 8);
-    c->B.act = (uint8_t*)((uintptr_t)X.act - (uintptr_t)lb);
-    c->B.foot = (u64*)((uintptr_t)X.foot - (uintptr_t)base * 8);
-    c->B.cls = (uint8_t*)((uintptr_t)X.cls - (uintptr_t)base);
-    // device links hold total_cap states: no store index may pass it
-    c->B.cap = X.dev_links ? std::min(base + X.win, X.total_cap) : base + X.win;
-}
-
-// Address space for the trace links of every state the set can hold; pages
-// are only backed once a spill touches them.
-int spill_reserve(rmc_ctx* c) {
-    SpillState& X = c->spill;
-    X.h_bytes = (size_t)X.total_cap * 9;
-    void* m = mmap(nullptr, X.h_bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    if (m == MAP_FAILED) {
-        X.h_bytes = 0;
-        return fail(c, RMC_E_NOMEM, "spill: cannot reserve host address space for the trace links");
-    }
-    (void)madvise(m, X.h_bytes, MADV_HUGEPAGE);  // 2 MiB faults: fewer, cheaper first touches
-    X.h_parent = (u64*)m;
-    X.h_act = (uint8_t*)m + (size_t)X.total_cap * 8;
-    X.faulted = 0;
-    return 0;
-}
-
-void spill_free(rmc_ctx* c) {
-    if (c->spill.ahead.joinable()) c->spill.ahead.join();
-    if (c->spill.h_bytes) munmap(c->spill.h_parent, c->spill.h_bytes);
-    c->spill.h_parent = nullptr;
-    c->spill.h_act = nullptr;
-    c->spill.h_bytes = 0;
-}
-
-// Touch fresh host pages from several threads: a device-to-host copy into
-// untouched pageable memory runs at page-fault speed (~13 GB/s measured),
-// into touched memory at ~48 GB/s (profiles/r02/host_link_rates.jsonl).
-static void prefault(void* p, size_t n) {
-    const int T = (int)std::min<size_t>(8, std::max<size_t>(1, n >> 26));
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([=] {  // one store per 4 KiB page backs it (fresh pages read as zero)
-            volatile char* q = (volatile char*)p;
-            for (size_t o = n * t / T, hi = n * (t + 1) / T; o < hi; o += 4096) q[o] = 0;
-        });
-    for (auto& x : th) x.join();
-}
-
-// Move the trace links of the device-resident states [base, a) to the host
-// and shift [a, count) to the start of the window.  (With the links in HBM the
-// window is a ring and nothing ever moves: see the launch loop.)
-int spill_to(rmc_ctx* c, u64 a, u64 count) {
-    SpillState& X = c->spill;
-    const u64 n = a - X.base;
-    if (!n) return 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    const u64 W = (u64)c->NW * 4;
-    u64* hp = X.h_parent + X.base;
-    uint8_t* ha = X.h_act + X.base;
-    if (X.ahead.joinable()) X.ahead.join();
-    if (a > X.faulted) {  // what the background touch did not reach
-        const u64 f0 = std::max(X.faulted, X.base);
-        prefault(X.h_parent + f0, (a - f0) * 8);
-        prefault(X.h_act + f0, a - f0);
-        X.faulted = a;
-    }
-    HIPCHK(c, hipMemcpyAsync(hp, X.parent, n * 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(ha, X.act, n, hipMemcpyDeviceToHost, c->st));
-    if (X.h_state) {  // verification: the states too (the window's first n are [base, a))
-        HIPCHK(c, hipMemcpyAsync(X.h_state + X.base * (u64)c->NW, X.store, n * W, hipMemcpyDeviceToHost, c->st));
-        X.hcopied = a;
-    }
-    // shift in pieces of at most n states: no piece overlaps its own destination,
-    // and stream order keeps every source read before a later piece overwrites it
-    const u64 m = count - a;
-    for (u64 off = 0; off < m; off += n) {
-        const u64 k = std::min(n, m - off);
-        HIPCHK(c, hipMemcpyAsync((char*)X.store + off * W, (char*)X.store + (n + off) * W, k * W,
-                                 hipMemcpyDeviceToDevice, c->st));
-        HIPCHK(c, hipMemcpyAsync(X.parent + off, X.parent + n + off, k * 8, hipMemcpyDeviceToDevice, c->st));
-        HIPCHK(c, hipMemcpyAsync(X.act + off, X.act + n + off, k, hipMemcpyDeviceToDevice, c->st));
-        HIPCHK(c, hipMemcpyAsync(X.foot + off, X.foot + n + off, k * 8, hipMemcpyDeviceToDevice, c->st));
-        HIPCHK(c, hipMemcpyAsync(X.cls + off, X.cls + n + off, k, hipMemcpyDeviceToDevice, c->st));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    spill_rebase(c, a);
-    // the next spill takes at most a window's worth: back those pages while the
-    // device expands
-    const u64 f1 = std::min(X.total_cap, a + X.win);
-    if (f1 > X.faulted) {
-        const u64 f0 = X.faulted;
-        X.faulted = f1;
-        X.ahead = std::thread([&X, f0, f1] {
-            prefault(X.h_parent + f0, (f1 - f0) * 8);
-            prefault(X.h_act + f0, f1 - f0);
-        });
-    }
-    c->res.spilled += n;
-    c->res.spills += 1;
-    c->res.spill_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return 0;
-}
-
-// ---- verification + spill --------------------------------------------------------
-// Full-state verification compares every fingerprint hit with the stored state
-// that owns the slot.  A spilled search overwrites (ring) or drops (shifted
-// window) the device copies of old states, so each state is copied to a host
-// mirror before its device copy goes, and a hit on such an owner is parked by
-// the expansion kernel (B.hbuf) and compared after the launch with the owner's
-// host copy (k_verify_host).  Most duplicates are of recent states, so few hits
-// take that path.
-int verify_spill_reserve(rmc_ctx* c) {
-    SpillState& X = c->spill;
-    X.hs_bytes = (size_t)X.total_cap * (size_t)c->NW * 4;
-    void* m = mmap(nullptr, X.hs_bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    if (m == MAP_FAILED) {
-        X.hs_bytes = 0;
-        return fail(c, RMC_E_NOMEM, "verification + spill: cannot reserve host address space for the states");
-    }
-    (void)madvise(m, X.hs_bytes, MADV_HUGEPAGE);
-    X.h_state = (u32*)m;
-    X.ostage_cap = 1ull << 22;
-    c->B.hcap = 1ull << 26;
-    if (hipHostMalloc(&X.h_ostage, X.ostage_cap * (u64)c->NW * 4, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&X.d_ostage, X.ostage_cap * (u64)c->NW * 4) != hipSuccess ||
-        hipMalloc(&c->B.hbuf, c->B.hcap * 16) != hipSuccess)
-        return fail(c, RMC_E_NOMEM, "verification + spill: staging allocation failed");
-    return 0;
-}
-
-// Ring window: copy the states [hcopied, upto) — all below the launch's frontier,
-// so final, and not yet overwritten — to the host mirror (up to two pieces).
-int verify_copy_out(rmc_ctx* c, u64 upto) {
-    SpillState& X = c->spill;
-    const u64 W = (u64)c->NW * 4;
-    while (X.hcopied < upto) {
-        const u64 i = X.hcopied, sl = i & c->B.wmask;
-        const u64 n = std::min(upto - i, X.win - sl);
-        HIPCHK(c, hipMemcpyAsync((char*)X.h_state + i * W, (char*)X.store + sl * W, n * W, hipMemcpyDeviceToHost,
-                                 c->st));
-        X.hcopied = i + n;
-    }
-    return 0;
-}
-
-// The n hits the last launch parked in B.hbuf {parent, owner index | lane << 56}:
-// stage the owners' host copies (batches of ostage_cap) and compare on the device.
-int verify_host_hits(rmc_ctx* c, u64 n) {
-    SpillState& X = c->spill;
-    if (n > c->B.hcap) return fail(c, RMC_E_CAPACITY, "verification buffer full");
-    std::vector<u64> rec(2 * n);
-    HIPCHK(c, hipMemcpyAsync(rec.data(), c->B.hbuf, n * 16, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    const u64 NW = (u64)c->NW;
-    for (u64 off = 0; off < n; off += X.ostage_cap) {
-        const u64 m = std::min(X.ostage_cap, n - off);
-        for (u64 q = 0; q < m; ++q) {
-            const u64 ix = rec[2 * (off + q) + 1] & ((1ull << 56) - 1);
-            if (ix >= X.hcopied)
-                return fail(c, RMC_E_HIP, "verification: a spilled owner (index " + std::to_string(ix) +
-                                              ") has no host copy");
-            memcpy(X.h_ostage + q * NW, X.h_state + ix * NW, NW * 4);
-        }
-        HIPCHK(c, hipMemcpyAsync(X.d_ostage, X.h_ostage, m * NW * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(c, launch(c->sh, Op::VerifyHost, c->P, c->PT, c->B, m, off, X.d_ostage, nullptr, 0, nullptr, c->st));
-        HIPCHK(c, hipStreamSynchronize(c->st));  // the pinned stage is refilled next
-    }
-    HIPCHK(c, hipMemsetAsync(&c->B.ctr->hcount, 0, 8, c->st));
-    c->h_ctr->hcount = 0;
-    X.host_hits += n;
-    return 0;
-}
-
-// The trace link (parent index, action lane) of any stored state.
-int read_link(rmc_ctx* c, u64 idx, u64* parent, uint8_t* act) {
-    if (c->spill.on && !c->spill.dev_links && idx < c->spill.base) {
-        *parent = c->spill.h_parent[idx];
-        *act = c->spill.h_act[idx];
-        return 0;
-    }
-    HIPCHK(c, hipMemcpy(parent, c->B.parent + idx, 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(act, c->B.act + idx, 1, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -761,19 +357,6 @@ void rmc_destroy(rmc_ctx* c) {
     delete c;
 }
 
-// The most new states one state's expansion can yield (rmc_plan.h
-// new_states_bound, never more than the lanes).  The spill window sizes its
-// launches by this bound (RMC_LANE_BOUND=0: every lane, the round-5 bound).
-static u64 max_new_per_state(const rmc_ctx* c) {
-    const u64 lanes = (u64)c->P.off[10];
-    static const bool all_lanes = [] {
-        const char* e = getenv("RMC_LANE_BOUND");
-        return e && atoi(e) == 0;
-    }();
-    if (all_lanes) return lanes;
-    return packed_new_states_bound(lanes, (u64)c->sh.S, (u64)c->P.V, (u64)(c->P.off[8] - c->P.off[7]));
-}
-
 // A fresh run (no rmc_recover before it): clear the result, the set and the
 // counters, and seed Init.  *depth: the level the loop starts from.
 static int start_run(rmc_ctx* c, int* depth) {
@@ -784,16 +367,8 @@ static int start_run(rmc_ctx* c, int* depth) {
     c->level_start.clear();
     if (c->spill.on) {
         spill_rebase(c, 0);
-        SpillState& X = c->spill;
-        const u64 f1 = std::min(X.total_cap, X.win);  // back the first spill's pages meanwhile
-        if (!X.dev_links && !X.ahead.joinable() && f1 > X.faulted) {
-            const u64 f0 = X.faulted;
-            X.faulted = f1;
-            X.ahead = std::thread([&X, f0, f1] {
-                prefault(X.h_parent + f0, (f1 - f0) * 8);
-                prefault(X.h_act + f0, f1 - f0);
-            });
-        }
+        SpillState& X = c->spill;  // back the first spill's pages meanwhile
+        if (!X.dev_links && !X.ahead.joinable()) spill_prefault_ahead(c, std::min(X.total_cap, X.win));
     }
     // The set epoch (raft_packed.h c_set_ep): a run on a ctx whose set holds the
     // tagged entries of an earlier run takes the next epoch and clears nothing —
@@ -821,13 +396,12 @@ static int start_run(rmc_ctx* c, int* depth) {
     init_view(c->cfg, &iv);
     std::vector<u32> packed((size_t)c->NW);
     std::string why;
-    if (encode_view(c, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
+    if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, launch(c->sh, Op::Seed, c->P, c->PT, c->B, 1, 0, c->d_staged, nullptr, 0, nullptr, c->st));
+    HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
     if (int rc = read_counters(c)) return rc;
     *depth = seed_done(c);
-    if (c->sh.verify)
-        HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, c->h_ctr->count, nullptr, nullptr, 0, nullptr, c->st));
+    if (c->sh.verify) HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
     return 0;
 }
 
@@ -917,20 +491,18 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 if (want == 0) return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
                 b = a + want;
             }
-            HIPCHK(c, launch(c->sh, Op::Expand, c->P, c->PT, c->B, a, b, nullptr, nullptr, 0, nullptr, c->st));
+            HIPCHK(c, launch(c, Op::Expand, a, b));
             c->res.expand_launches += 1;
             if (c->sh.sym && !c->sh.verify) {
-                HIPCHK(c, launch(c->sh, Op::Ties, c->P, c->PT, c->B, 0, 0, nullptr, nullptr, 0, nullptr, c->st));
+                HIPCHK(c, launch(c, Op::Ties));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
             }
             if (c->sh.verify) {
                 const u64 before = c->h_ctr->count;
                 if (int rc = read_counters(c)) return rc;
                 if (c->h_ctr->overflow) break;
-                HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, before, c->h_ctr->count, nullptr, nullptr, 0, nullptr,
-                                 c->st));
-                HIPCHK(c, launch(c->sh, Op::Verify, c->P, c->PT, c->B, c->h_ctr->vcount, 0, nullptr, nullptr, 0, nullptr,
-                                 c->st));
+                HIPCHK(c, launch(c, Op::Publish, before, c->h_ctr->count));
+                HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
                 c->h_ctr->vcount = 0;
                 if (c->h_ctr->hcount)  // hits on spilled owners: against their host copies
@@ -987,236 +559,6 @@ int rmc_get_result(const rmc_ctx* c, rmc_result* out) {
     return 0;
 }
 
-// ---- checkpoint / recovery (TLC -checkpoint / -recover) ------------------------
-// File: header, level boundaries, then the stored states, parent refs and lanes
-// of levels 1..depth.  The fingerprint set is not written: rmc_recover rebuilds
-// it from the states (k_rehash), one pass over the store.
-namespace {
-// The header embeds the ABI structs rmc_config and rmc_result, so its size is
-// written too and must match: a struct that grows changes kCkptVersion.
-constexpr uint32_t kCkptVersion = 5;  // 3: rmc_result with parked / exchange_wait_seconds; 4: the set holds
-                                      // k ^ s values (raft_packed.h Fp), rmc_result with spill_links_on_device;
-                                      // 5: rmc_config.set_bytes, rmc_result.verified_spilled
-struct CkptHeader {
-    char magic[8];
-    uint32_t version, nw;
-    uint32_t header_bytes, pad_;
-    rmc_config cfg;
-    uint64_t count, nlevels;
-    int32_t depth;
-    int32_t shard;   // sharded checkpoint: rank | world << 16 (0: single GPU)
-    rmc_result res;
-    uint64_t first;  // states are written from this index on (0: all; else the frontier)
-    uint64_t slots;  // fingerprint-set slots dumped after the states (first > 0), else 0
-};
-const char kCkptMagic[8] = {'R', 'M', 'C', 'C', 'K', 'P', 'T', '1'};
-
-bool same_model(const rmc_config& a, const rmc_config& b) {
-    return a.n_servers == b.n_servers && a.n_values == b.n_values && a.max_term == b.max_term &&
-           a.max_log_len == b.max_log_len && a.max_msgs == b.max_msgs && a.max_dup == b.max_dup &&
-           ((a.flags ^ b.flags) & ~RMC_FLAG_SPILL) == 0 && a.invariants == b.invariants && a.seed == b.seed;
-}
-
-// Copy n bytes between a device buffer and a file through a pinned bounce buffer.
-int move_file(rmc_ctx* c, FILE* f, void* dev, u64 n, bool to_file) {
-    const u64 B = 64ull << 20;
-    void* h = nullptr;
-    HIPCHK(c, hipHostMalloc(&h, B, hipHostMallocDefault));
-    int rc = 0;
-    for (u64 off = 0; off < n && !rc; off += B) {
-        const u64 k = std::min(B, n - off);
-        char* d = (char*)dev + off;
-        if (to_file) {
-            if (hipMemcpy(h, d, k, hipMemcpyDeviceToHost) != hipSuccess) rc = RMC_E_HIP;
-            else if (fwrite(h, 1, k, f) != k) rc = fail(c, RMC_E_IO, "checkpoint write failed");
-        } else {
-            if (fread(h, 1, k, f) != k) rc = fail(c, RMC_E_IO, "checkpoint file truncated");
-            else if (hipMemcpy(d, h, k, hipMemcpyHostToDevice) != hipSuccess) rc = RMC_E_HIP;
-        }
-    }
-    (void)hipHostFree(h);
-    if (rc == RMC_E_HIP) return fail(c, rc, "checkpoint copy failed");
-    return rc;
-}
-}  // namespace
-
-// Layout: header, level table, parent[0, count), act[0, count), store[first,
-// count), then — when the states below `first` have spilled and no longer
-// exist — the fingerprint set itself (TLC checkpoints its FPSet too).
-int rmc_checkpoint(rmc_ctx* c, const char* path) {
-    if (!c || !path) return RMC_E_INVAL;
-    if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
-    if (c->level_start.size() < 2 || c->have_target)
-        return fail(c, RMC_E_STATE, "checkpoint: needs a BFS stopped at a level boundary without a violation");
-    if (c->res.left_on_queue == 0) return fail(c, RMC_E_STATE, "checkpoint: the search is complete");
-    if (c->spill.on && c->sh.verify)
-        return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_VERIFY_STATES and RMC_FLAG_SPILL "
-                                    "(the host copies of the spilled states are not written)");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    // a sharded search: every rank writes its own part, <path>.rank<r> (collective
-    // only in the sense that every rank calls it; the global counts ride in res)
-    const std::string file = shard_path(c, path);
-    FILE* f = fopen(file.c_str(), "wb");
-    if (!f) return fail(c, RMC_E_IO, "checkpoint: cannot create " + file);
-    CkptHeader h{};
-    h.shard = c->dist.on ? (c->dist.rank | (c->dist.world << 16)) : 0;
-    memcpy(h.magic, kCkptMagic, 8);
-    h.version = kCkptVersion;
-    h.header_bytes = (uint32_t)sizeof(CkptHeader);
-    h.nw = (uint32_t)c->NW;
-    h.cfg = c->cfg;
-    h.count = c->level_start.back();
-    h.nlevels = c->level_start.size();
-    h.depth = c->res.depth;
-    h.res = c->res;
-    const u64 base = c->spill.on ? c->spill.base : 0;
-    h.first = base ? c->level_start[h.nlevels - 2] : 0;  // >= base at a level boundary
-    h.slots = base ? c->table_slots : 0;
-    h.pad_ = h.slots ? c->set_epoch : 0;  // the dumped set's epoch tag (0: untagged)
-    int rc = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(c->level_start.data(), 8, h.nlevels, f) == h.nlevels
-                 ? 0 : fail(c, RMC_E_IO, "checkpoint write failed");
-    auto put = [&](const void* p, u64 n) {
-        if (!rc && n && fwrite(p, 1, n, f) != n) rc = fail(c, RMC_E_IO, "checkpoint write failed");
-    };
-    const u64 lb = c->spill.dev_links ? 0 : base;  // links below lb are on the host
-    const u64 nd = h.count - lb;
-    if (lb) put(c->spill.h_parent, lb * 8);
-    if (!rc) rc = move_file(c, f, c->B.parent + lb, nd * 8, true);
-    if (lb) put(c->spill.h_act, lb);
-    if (!rc) rc = move_file(c, f, c->B.act + lb, nd, true);
-    for (u64 i = h.first; !rc && i < h.count;) {  // the ring window: in up to two pieces
-        const u64 sl = wslot(c->B, i), n = std::min(h.count - i, c->B.wmask == ~0ull ? h.count - i : c->spill.win - sl);
-        rc = move_file(c, f, c->B.store + sl * (u64)c->NW, n * (u64)c->NW * 4, true);
-        i += n;
-    }
-    if (!rc && h.slots) rc = move_file(c, f, c->B.table, h.slots * 8, true);
-    if (fclose(f) != 0 && !rc) rc = fail(c, RMC_E_IO, "checkpoint close failed");
-    return rc;
-}
-
-int rmc_recover(rmc_ctx* c, const char* path) {
-    if (!c || !path) return RMC_E_INVAL;
-    if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
-    if (c->spill.on && c->sh.verify)
-        return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_VERIFY_STATES and RMC_FLAG_SPILL");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const std::string file = shard_path(c, path);
-    FILE* f = fopen(file.c_str(), "rb");
-    if (!f) return fail(c, RMC_E_IO, "recover: cannot open " + file);
-    CkptHeader h{};
-    int rc = 0;
-    std::vector<u64> ls;
-    // the fixed prefix first (magic, version): an older version is refused by
-    // name before its differently laid-out remainder is interpreted
-    const size_t pre = offsetof(CkptHeader, header_bytes);
-    if (fread(&h, pre, 1, f) != 1 || memcmp(h.magic, kCkptMagic, 8) != 0)
-        rc = fail(c, RMC_E_IO, "recover: not an rmc checkpoint");
-    else if (h.version != kCkptVersion)
-        rc = fail(c, RMC_E_IO, "recover: checkpoint format version " + std::to_string(h.version) +
-                                   " (this build reads version " + std::to_string(kCkptVersion) +
-                                   "); recreate the checkpoint with this build");
-    else if (fread((char*)&h + pre, sizeof h - pre, 1, f) != 1 || h.header_bytes != (uint32_t)sizeof(CkptHeader))
-        rc = fail(c, RMC_E_IO, "recover: checkpoint header truncated or of another layout");
-    else if (h.shard != (c->dist.on ? (c->dist.rank | (c->dist.world << 16)) : 0))
-        rc = fail(c, RMC_E_INVAL, "recover: the checkpoint is of another shard layout (rank / world), or of a "
-                                  "single-GPU run recovered on a sharded ctx or the reverse");
-    else if (h.nw != (uint32_t)c->NW || !same_model(h.cfg, c->cfg))
-        rc = fail(c, RMC_E_INVAL, "recover: the checkpoint is of another model (constants, bounds, flags or seed)");
-    else if (h.first && (!c->spill.on || h.slots != c->table_slots))
-        rc = fail(c, RMC_E_INVAL, "recover: a spilled checkpoint holds the fingerprint set, not the spilled "
-                                  "states; recover it with RMC_FLAG_SPILL and the same state_capacity");
-    else {
-        ls.resize(h.nlevels);
-        if (h.nlevels < 2 || fread(ls.data(), 8, h.nlevels, f) != h.nlevels || ls.back() != h.count ||
-            h.first > h.count)
-            rc = fail(c, RMC_E_IO, "recover: corrupt level table");
-    }
-    // states [0, s) keep only their trace links, on the host (spill mode, when
-    // they do not all fit the window); [s, count) — at least the frontier — go
-    // to the device
-    u64 s = 0;
-    if (!rc) {
-        s = h.first ? h.first : (c->spill.on && h.count > c->spill.win) ? ls[ls.size() - 2] : 0;
-        const u64 room = c->spill.on ? c->spill.win : c->B.cap;
-        if (h.count - s > room || (c->spill.on && h.count > c->spill.total_cap))
-            rc = fail(c, RMC_E_CAPACITY, "recover: the checkpoint holds more states than this ctx's capacity");
-        if (!rc && !h.first && s && h.count - s >= room)  // no room left to stream the rehash through
-            rc = fail(c, RMC_E_CAPACITY, "recover: the frontier fills the device window");
-    }
-    if (rc) {
-        fclose(f);
-        return rc;
-    }
-    if (c->spill.on) {
-        if (c->spill.ahead.joinable()) c->spill.ahead.join();  // it may be touching [0, s)
-        spill_rebase(c, 0);
-        if (!c->spill.dev_links) c->spill.faulted = std::max(c->spill.faulted, s);  // fread backs the links it writes
-    }
-    const u64 NW = (u64)c->NW, W = NW * 4;
-    u32* dstore = c->spill.on ? c->spill.store : c->B.store;
-    u64* dparent = c->spill.on ? c->spill.parent : c->B.parent;
-    uint8_t* dact = c->spill.on ? c->spill.act : c->B.act;
-    auto get = [&](void* p, u64 n) {
-        if (!rc && n && fread(p, 1, n, f) != n) rc = fail(c, RMC_E_IO, "checkpoint file truncated");
-    };
-    HIPCHK(c, launch_fill(c->B.table, c->table_slots * 8, 0, c->st));
-    if (c->sh.verify) HIPCHK(c, launch_fill(c->B.sidx, c->table_slots * 8, 0xFF, c->st));
-    // footprints are not checkpointed: the recovered frontier is expanded without
-    // diamond skipping (FOOT_VALID clear), the levels after it with
-    HIPCHK(c, hipMemsetAsync(c->spill.on ? c->spill.foot : c->B.foot, 0,
-                             (c->spill.on ? c->spill.win : c->B.cap) * 8, c->st));
-    // a dumped set keeps its entries' epoch tag (header pad_); states rehashed
-    // below go into an untagged set
-    c->set_epoch = h.slots ? std::min<u32>(h.pad_, 255u) : 0u;
-    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
-    if (int r2 = reset_counters(c, false)) return r2;
-    const u64 ls0 = c->spill.dev_links ? 0 : s;  // links below ls0 go to the host
-    if (ls0) get(c->spill.h_parent, ls0 * 8);
-    if (!rc) rc = move_file(c, f, dparent, (h.count - ls0) * 8, false);
-    if (ls0) get(c->spill.h_act, ls0);
-    if (!rc) rc = move_file(c, f, dact, h.count - ls0, false);
-    if (!h.first && s && !rc) {
-        // no set in the file: rehash the states below s through the free part
-        // of the window (the frontier is loaded after them, at its start)
-        const u64 piece = c->spill.win - (h.count - s);
-        u32* area = dstore + (h.count - s) * NW;
-        for (u64 p = 0; p < s && !rc; p += piece) {
-            const u64 k = std::min(piece, s - p);
-            rc = move_file(c, f, area, k * W, false);
-            DevBufs T = c->B;
-            T.store = (u32*)((uintptr_t)area - (uintptr_t)(p * W));
-            T.wmask = ~0ull;  // indexed through the biased pointer, not the ring
-            if (!rc) HIPCHK(c, launch(c->sh, Op::Rehash, c->P, c->PT, T, p, p + k, nullptr, nullptr, 0, nullptr, c->st));
-            if (!rc) HIPCHK(c, hipStreamSynchronize(c->st));
-        }
-    }
-    if (c->spill.on && c->spill.dev_links) {  // the ring window: state i at slot i & wmask
-        const u64 win = c->spill.win;
-        for (u64 i = s; !rc && i < h.count;) {
-            const u64 sl = i & (win - 1), n = std::min(h.count - i, win - sl);
-            rc = move_file(c, f, dstore + sl * NW, n * W, false);
-            i += n;
-        }
-    } else if (!rc) {
-        rc = move_file(c, f, dstore, (h.count - s) * W, false);
-    }
-    if (!rc && h.slots) rc = move_file(c, f, c->B.table, h.slots * 8, false);
-    fclose(f);
-    if (rc) return rc;
-    if (s) spill_rebase(c, s);
-    if (!h.slots) HIPCHK(c, launch(c->sh, Op::Rehash, c->P, c->PT, c->B, s, h.count, nullptr, nullptr, 0, nullptr, c->st));
-    if (c->sh.verify) HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, h.count, nullptr, nullptr, 0, nullptr, c->st));
-    if (int r2 = read_counters(c)) return r2;
-    if (c->h_ctr->table_full) return fail(c, RMC_E_CAPACITY, "recover: fingerprint set full");
-    if (c->h_ctr->overflow) return fail(c, RMC_E_IO, "recover: the checkpoint holds duplicate states");
-    c->level_start = ls;
-    c->res = h.res;
-    c->resume = 1;
-    c->resume_depth = h.depth;
-    return 0;
-}
-
 // The counterexample: parent links back to Init, then the states.  States
 // whose store was spilled are re-derived by replaying the recorded lanes from
 // the last state still known (Init at worst) with the listing kernel — the
@@ -1229,231 +571,53 @@ int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* in
     if (c->dist.on) return trace_sharded(c, states, families, instances, cap, len);
     std::vector<u64> chain;
     std::vector<uint8_t> acts;
-    u64 idx = c->target_idx;
-    for (;;) {
-        u64 p = 0;
-        uint8_t a = 0;
-        if (int rc = read_link(c, idx, &p, &a)) return rc;
-        chain.push_back(idx);
-        acts.push_back(a);
-        if (p == ~0ull || chain.size() > 100000) break;
-        idx = p;
-    }
-    std::reverse(chain.begin(), chain.end());
-    std::reverse(acts.begin(), acts.end());
+    if (int rc = walk_links(c, [c](u64 i, u64* p, uint8_t* a) { return read_link(c, i, p, a); }, &chain, &acts)) return rc;
     *len = chain.size();
     const u64 NW = (u64)c->NW, RW = 6 + NW, lanes = (u64)c->P.off[10];
     std::vector<u32> cur(NW);
-    u32 *d_in = nullptr, *d_out = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    int rc = 0;
-    for (size_t q = 0; q < chain.size() && !rc; ++q) {
+    DevScratch<u32> d_in, d_out;  // replay buffers, allocated by the first replayed state
+    DevScratch<unsigned long long> d_cnt;
+    for (size_t q = 0; q < chain.size(); ++q) {
         if (!c->spill.on || chain[q] >= c->spill.base) {
             HIPCHK(c, hipMemcpy(cur.data(), c->B.store + wslot(c->B, chain[q]) * NW, NW * 4, hipMemcpyDeviceToHost));
         } else if (q == 0) {  // Init (raft.tla:125-129), the one initial state
             rmc_state_view iv;
             init_view(c->cfg, &iv);
             std::string why;
-            if (encode_view(c, iv, cur.data(), &why)) return fail(c, RMC_E_INVAL, why);
+            if (encode_view(c->sh.S, c->sh.K, iv, cur.data(), &why)) return fail(c, RMC_E_INVAL, why);
         } else {  // replay lane acts[q] from the previous state on the device
-            if (!d_in) {
-                if (hipMalloc(&d_in, NW * 4) != hipSuccess || hipMalloc(&d_out, lanes * RW * 4) != hipSuccess ||
-                    hipMalloc(&d_cnt, 8) != hipSuccess)
-                    rc = fail(c, RMC_E_NOMEM, "trace: replay buffers");
-            }
+            if (!d_in.get() && (d_in.alloc(NW) != hipSuccess || d_out.alloc(lanes * RW) != hipSuccess ||
+                                d_cnt.alloc(1) != hipSuccess))
+                return fail(c, RMC_E_NOMEM, "trace: replay buffers");
             std::vector<u32> recs(lanes * RW);
             unsigned long long n = 0;
-            if (!rc && (hipMemcpy(d_in, cur.data(), NW * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemset(d_cnt, 0, 8) != hipSuccess ||
-                        launch(c->sh, Op::List, c->P, c->PT, c->B, 1, 0, d_in, d_out, lanes, d_cnt, c->st) != hipSuccess ||
-                        hipStreamSynchronize(c->st) != hipSuccess ||
-                        hipMemcpy(&n, d_cnt, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(recs.data(), d_out, std::min<u64>(n, lanes) * RW * 4, hipMemcpyDeviceToHost) != hipSuccess))
-                rc = fail(c, RMC_E_HIP, "trace: replay launch failed");
+            if (hipMemcpy(d_in.get(), cur.data(), NW * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemset(d_cnt.get(), 0, 8) != hipSuccess ||
+                launch(c, Op::List, 1, 0, d_in.get(), d_out.get(), lanes, d_cnt.get()) != hipSuccess ||
+                hipStreamSynchronize(c->st) != hipSuccess ||
+                hipMemcpy(&n, d_cnt.get(), 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(recs.data(), d_out.get(), std::min<u64>(n, lanes) * RW * 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(c, RMC_E_HIP, "trace: replay launch failed");
             bool found = false;
-            for (u64 r = 0; !rc && r < std::min<u64>(n, lanes); ++r) {
+            for (u64 r = 0; r < std::min<u64>(n, lanes) && !found; ++r) {
                 const u32* rec = &recs[r * RW];
-                if (rec[2] == acts[q] && rec[3]) {
-                    memcpy(cur.data(), rec + 6, NW * 4);
-                    found = true;
-                    break;
-                }
+                found = rec[2] == acts[q] && rec[3];
+                if (found) memcpy(cur.data(), rec + 6, NW * 4);
             }
-            if (!rc && !found) rc = fail(c, RMC_E_STATE, "trace: a recorded lane is not enabled on replay");
+            if (!found) return fail(c, RMC_E_STATE, "trace: a recorded lane is not enabled on replay");
         }
-        if (!rc && q < cap) {
-            if (states) decode_state(c, cur.data(), &states[q]);
-            if (families) families[q] = family_of(c->P, acts[q]);
-            if (instances) instances[q] = acts[q] == 255 ? -1 : acts[q];
+        if (q < cap) {
+            if (states) decode_state(c->sh.S, c->sh.K, cur.data(), &states[q]);
+            fill_step(families, instances, q, family_of(c->P, acts[q]), acts[q]);
         }
     }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_cnt);
-    return rc;
+    return 0;
 }
 
 }  // extern "C"
 
-// ---- simulation: SmokeInit sampler (Smokeraft.tla:4-76) and random walks -------
+// ---- simulation: random walks from Init or SmokeInit (rmc_codec.cpp) -----------
 namespace {
-
-// RandomSubset(k, X): k distinct random elements of X, X given by a sampler.
-template <class T, class F>
-std::vector<T> random_subset(int k, F draw, std::mt19937_64& g) {
-    std::vector<T> out;
-    for (int guard = 0; (int)out.size() < k && guard < 100000; ++guard) {
-        T x = draw(g);
-        if (std::find(out.begin(), out.end(), x) == out.end()) out.push_back(x);
-    }
-    return out;
-}
-
-struct SmokeDomains {
-    int S, V, nat;
-    int uni(std::mt19937_64& g, int lo, int hi) const {  // uniform in lo..hi
-        return lo + (int)(g() % (u64)(hi - lo + 1));
-    }
-    // BoundedSeq([term : SmokeNat, value : Value], n) (Smokeraft.tla:4-6): uniform over
-    // the whole set of sequences of length 0..n; encoded as (len, e0, e1, ...).
-    std::vector<int> seq(std::mt19937_64& g, int n) const {
-        const u64 E = (u64)(nat + 1) * (u64)V;
-        u64 total = 0, p = 1;
-        for (int m = 0; m <= n; ++m, p *= E) total += p;
-        u64 r = g() % total;
-        int len = 0;
-        p = 1;
-        while (r >= p) { r -= p; p *= E; ++len; }
-        std::vector<int> s{len};
-        for (int x = 0; x < len; ++x) {
-            const u64 e = r % E;
-            r /= E;
-            s.push_back((int)(e / (u64)V));  // term
-            s.push_back((int)(e % (u64)V));  // value
-        }
-        return s;
-    }
-};
-
-// One message of SmokeMessageType (Smokeraft.tla:24-62) as a canonical int vector.
-std::vector<int> smoke_msg(const SmokeDomains& D, int type, std::mt19937_64& g) {
-    std::vector<int> v{type, D.uni(g, 0, D.nat), D.uni(g, 0, D.S - 1), D.uni(g, 0, D.S - 1)};
-    if (type == RVQ) { v.push_back(D.uni(g, 0, D.nat)); v.push_back(D.uni(g, 0, D.nat)); }
-    if (type == AEQ) {
-        v.push_back(D.uni(g, -1, 1));              // mprevLogIndex \in SmokeInt
-        v.push_back(D.uni(g, 0, D.nat));           // mprevLogTerm
-        const auto e = D.seq(g, 1);                // mentries \in SmokeSeq(...)
-        v.insert(v.end(), e.begin(), e.end());
-        v.push_back(D.uni(g, 0, D.nat));           // mcommitIndex
-    }
-    if (type == RVP) {
-        v.push_back(D.uni(g, 0, 1));               // mvoteGranted \in BOOLEAN
-        const auto e = D.seq(g, 1);                // mlog \in SmokeSeq(...)
-        v.insert(v.end(), e.begin(), e.end());
-    }
-    if (type == AEP) { v.push_back(D.uni(g, 0, 1)); v.push_back(D.uni(g, 0, D.nat)); }
-    return v;
-}
-
-void msg_to_view(const std::vector<int>& v, rmc_msg_view* m) {
-    memset(m, 0, sizeof *m);
-    m->mtype = v[0];
-    m->mterm = v[1];
-    m->msource = v[2];
-    m->mdest = v[3];
-    m->count = 1;
-    size_t p = 4;
-    auto seq = [&](rmc_entry* out, int32_t* len) {
-        *len = v[p++];
-        for (int x = 0; x < *len; ++x) { out[x].term = v[p++]; out[x].value = v[p++]; }
-    };
-    if (v[0] == RVQ) { m->mlastLogTerm = v[p++]; m->mlastLogIndex = v[p++]; }
-    if (v[0] == AEQ) { m->mprevLogIndex = v[p++]; m->mprevLogTerm = v[p++]; seq(m->mentries, &m->mentries_len); m->mcommitIndex = v[p++]; }
-    if (v[0] == RVP) { m->mvoteGranted = v[p++]; seq(m->mlog, &m->mlog_len); }
-    if (v[0] == AEP) { m->msuccess = v[p++]; m->mmatchIndex = v[p++]; }
-}
-
-// SmokeInit (Smokeraft.tla:64-76): k choices for each of the 9 per-server
-// variables, all k^9 combinations, each with the same bag of k messages drawn as
-// [RandomSubset(k, SmokeMessageType) -> {1}].
-}  // namespace
-
-namespace rmc_host {
-// SmokeInit (Smokeraft.tla:64-76) as k^9 views, in RandomSubset product order.
-int smoke_views(const rmc_ctx* c, const rmc_sim_config& sc, std::vector<rmc_state_view>* views, std::string* why) {
-    const int S = c->cfg.n_servers, k = sc.smoke_k;
-    SmokeDomains D{S, c->cfg.n_values, sc.smoke_nat > 0 ? sc.smoke_nat : 2};
-    if (D.nat > 3 && !c->wide) { *why = "smoke_nat > 3 exceeds the packed index range"; return RMC_E_INVAL; }
-    if (D.nat > 100) { *why = "smoke_nat > 100"; return RMC_E_INVAL; }
-    const int bag = c->wide ? rmc::wide::KW : c->sh.K;
-    if (k > bag) { *why = "smoke_k messages exceed the bag capacity (set MaxMsgs >= k)"; return RMC_E_INVAL; }
-    std::mt19937_64 g(sc.seed ^ 0x5350AC3ull);
-    using V = std::vector<int>;
-    auto fn = [&](auto elem) { return [&, elem](std::mt19937_64& gg) { V v; for (int i = 0; i < S; ++i) { auto e = elem(gg); v.insert(v.end(), e.begin(), e.end()); } return v; }; };
-    auto one = [&](int lo, int hi) { return [&D, lo, hi](std::mt19937_64& gg) { return V{D.uni(gg, lo, hi)}; }; };
-    const auto ct = random_subset<V>(k, fn(one(0, D.nat)), g);                               // :67
-    const auto st = random_subset<V>(k, fn(one(0, 2)), g);                                   // :68
-    const auto vf = random_subset<V>(k, fn(one(-1, S - 1)), g);                              // :69 (Nil = -1)
-    const auto lg = random_subset<V>(k, fn([&](std::mt19937_64& gg) { return D.seq(gg, 3); }), g);  // :70
-    const auto ci = random_subset<V>(k, fn(one(0, D.nat)), g);                               // :71
-    const auto vr = random_subset<V>(k, fn(one(0, (1 << S) - 1)), g);                        // :72
-    const auto vg = random_subset<V>(k, fn(one(0, (1 << S) - 1)), g);                        // :73
-    auto row = [&](int lo, int hi) { return [&, lo, hi](std::mt19937_64& gg) { V v; for (int j = 0; j < S; ++j) v.push_back(D.uni(gg, lo, hi)); return v; }; };
-    const auto ni = random_subset<V>(k, fn(row(1, D.nat)), g);                               // :74
-    const auto mi = random_subset<V>(k, fn(row(0, D.nat)), g);                               // :75
-    std::vector<V> mtype_union;                                                              // :58-62
-    for (int t : {RVQ, AEQ, RVP, AEP}) {
-        auto part = random_subset<V>(k, [&, t](std::mt19937_64& gg) { return smoke_msg(D, t, gg); }, g);
-        mtype_union.insert(mtype_union.end(), part.begin(), part.end());
-    }
-    const auto msgs = random_subset<V>(k, [&](std::mt19937_64& gg) { return mtype_union[gg() % mtype_union.size()]; }, g);  // :76
-    for (const auto* vec : {&ct, &st, &vf, &lg, &ci, &vr, &vg, &ni, &mi})
-        if ((int)vec->size() != k) { *why = "RandomSubset could not draw k distinct elements"; return RMC_E_INVAL; }
-    u64 n = 1;
-    for (int x = 0; x < 9; ++x) n *= (u64)k;
-    views->assign(n, rmc_state_view{});
-    for (u64 idx = 0; idx < n; ++idx) {
-        int dg[9];
-        u64 r = idx;
-        for (int x = 0; x < 9; ++x) { dg[x] = (int)(r % (u64)k); r /= (u64)k; }
-        rmc_state_view v;
-        memset(&v, 0, sizeof v);
-        v.n_servers = S;
-        size_t lp = 0;
-        for (int i = 0; i < S; ++i) {
-            v.currentTerm[i] = ct[dg[0]][i];
-            v.state[i] = st[dg[1]][i];
-            v.votedFor[i] = vf[dg[2]][i];
-            v.commitIndex[i] = ci[dg[4]][i];
-            v.votesResponded[i] = (uint32_t)vr[dg[5]][i];
-            v.votesGranted[i] = (uint32_t)vg[dg[6]][i];
-            for (int j = 0; j < S; ++j) {
-                v.nextIndex[i][j] = ni[dg[7]][i * S + j];
-                v.matchIndex[i][j] = mi[dg[8]][i * S + j];
-            }
-        }
-        const V& L = lg[dg[3]];
-        for (int i = 0; i < S; ++i) {
-            v.log_len[i] = L[lp++];
-            for (int x = 0; x < v.log_len[i]; ++x) { v.log[i][x].term = L[lp++]; v.log[i][x].value = L[lp++]; }
-        }
-        v.n_msgs = (int)msgs.size();
-        for (size_t q = 0; q < msgs.size(); ++q) msg_to_view(msgs[q], &v.msgs[q]);
-        (*views)[idx] = v;
-    }
-    return 0;
-}
-}  // namespace rmc_host
-
-namespace {
-int smoke_init(const rmc_ctx* c, const rmc_sim_config& sc, std::vector<u32>* packed, std::string* why) {
-    std::vector<rmc_state_view> views;
-    if (int rc = smoke_views(c, sc, &views, why)) return rc;
-    packed->assign(views.size() * (u64)c->NW, 0u);
-    for (size_t q = 0; q < views.size(); ++q)
-        if (int rc = encode_view(c, views[q], packed->data() + q * (u64)c->NW, why)) return rc;
-    return 0;
-}
 
 int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_beh, std::vector<u32>* rec,
             std::vector<rmc_state_view>* wrec = nullptr) {
@@ -1468,12 +632,12 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
     std::vector<u32> inits;
     std::string why;
     if (sc->smoke_k > 0) {
-        if (int rc = smoke_init(c, *sc, &inits, &why)) return fail(c, rc, why);
+        if (int rc = smoke_init(smoke_shape(c->cfg, false), *sc, &inits, &why)) return fail(c, rc, why);
     } else {
         rmc_state_view iv;
         init_view(c->cfg, &iv);
         inits.assign((size_t)c->NW, 0u);
-        if (int rc = encode_view(c, iv, inits.data(), &why)) return fail(c, rc, why);
+        if (int rc = encode_view(c->sh.S, c->sh.K, iv, inits.data(), &why)) return fail(c, rc, why);
     }
     const u64 n_init = inits.size() / (u64)c->NW;
     // The model's bounds, as TLC's simulator respects a state CONSTRAINT; a
@@ -1482,42 +646,24 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
     // what a state can hold.
     Params P = c->P;
     P.max_msgs = std::min(P.max_msgs, c->sh.K);
-    u32 *d_init = nullptr, *d_rec = nullptr;
-    SimCounters* d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_init, inits.size() * 4));
-    HIPCHK(c, hipMalloc(&d_out, sizeof(SimCounters)));
-    if (rec) HIPCHK(c, hipMalloc(&d_rec, (size_t)sc->depth * c->NW * 4));
-    SimCounters h{};
-    h.viol = ~0ull;
-    HIPCHK(c, hipMemcpy(d_init, inits.data(), inits.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_out, &h, sizeof h, hipMemcpyHostToDevice));
-    HIPCHK(c, hipEventRecord(c->ev0, c->st));
-    HIPCHK(c, launch_sim(c->sh, P, d_init, n_init, sc->behaviours, sc->depth, sc->seed, sc->mode, d_out, rec_beh, d_rec, c->st));
-    HIPCHK(c, hipEventRecord(c->ev1, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
+    DevScratch<u32> d_init, d_rec;
+    DevScratch<SimCounters> d_out;
+    HIPCHK(c, d_init.alloc(inits.size()));
+    HIPCHK(c, d_out.alloc(1));
+    if (rec) HIPCHK(c, d_rec.alloc((size_t)sc->depth * c->NW));
+    HIPCHK(c, hipMemcpy(d_init.get(), inits.data(), inits.size() * 4, hipMemcpyHostToDevice));
+    SimCounters h;
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    HIPCHK(c, hipMemcpy(&h, d_out, sizeof h, hipMemcpyDeviceToHost));
+    if (int rc = sim_timed(c, d_out.get(), &h, &ms, [&] {
+            return launch_sim(c->sh, P, d_init.get(), n_init, sc->behaviours, sc->depth, sc->seed, sc->mode, d_out.get(),
+                              rec_beh, d_rec.get(), c->st);
+        }))
+        return rc;
     if (rec) {
         rec->assign((size_t)(h.steps + 1) * c->NW, 0u);
-        HIPCHK(c, hipMemcpy(rec->data(), d_rec, rec->size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(rec->data(), d_rec.get(), rec->size() * 4, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_init);
-    (void)hipFree(d_out);
-    (void)hipFree(d_rec);
-    memset(out, 0, sizeof *out);
-    out->behaviours = rec ? 1 : sc->behaviours;
-    out->steps = h.steps;
-    out->init_states = n_init;
-    out->truncated = h.truncated;
-    out->deadlocked = h.deadlocked;
-    if (h.viol != ~0ull) {
-        out->violated_inv = 1 << (int)((h.viol >> 40) & 15);
-        out->violation_depth = (int32_t)(h.viol >> 44);
-        out->violation_behaviour = h.viol & ((1ull << 40) - 1);
-    }
-    out->kernel_seconds = 1e-3 * ms;
-    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fill_sim_result(out, h, rec ? 1 : sc->behaviours, n_init, ms, t0);
     return 0;
 }
 
@@ -1531,20 +677,20 @@ int rmc_smoke_init(const rmc_config* cfg, const rmc_sim_config* sc, rmc_state_vi
     if (!cfg || !sc || !n || sc->smoke_k < 1) return RMC_E_INVAL;
     std::string why;
     if (validate(cfg, &why)) return RMC_E_INVAL;
-    rmc_ctx host;  // codec only: no device, no allocation
-    host.cfg = *cfg;
-    fill_params(&host);
-    if (host.wide) {
+    const SmokeShape m = smoke_shape(*cfg, wide_wanted(*cfg));
+    if (m.wide) {
         std::vector<rmc_state_view> views;
-        if (smoke_views(&host, *sc, &views, &why)) return RMC_E_INVAL;
+        if (smoke_views(m, *sc, &views, &why)) return RMC_E_INVAL;
         *n = views.size();
         for (size_t q = 0; q < *n && q < cap && states; ++q) states[q] = views[q];
         return 0;
     }
     std::vector<u32> packed;
-    if (smoke_init(&host, *sc, &packed, &why)) return RMC_E_INVAL;
-    *n = packed.size() / (size_t)host.NW;
-    for (size_t q = 0; q < *n && q < cap && states; ++q) decode_state(&host, packed.data() + q * host.NW, &states[q]);
+    if (smoke_init(m, *sc, &packed, &why)) return RMC_E_INVAL;
+    const size_t NW = (size_t)(2 * m.n_servers + m.bag);
+    *n = packed.size() / NW;
+    for (size_t q = 0; q < *n && q < cap && states; ++q)
+        decode_state(m.n_servers, m.bag, packed.data() + q * NW, &states[q]);
     return 0;
 }
 
@@ -1562,7 +708,7 @@ int rmc_sim_replay(rmc_ctx* c, const rmc_sim_config* sc, uint64_t behaviour, rmc
     }
     if (int rc = run_sim(c, sc, &r, (i64)behaviour, &rec)) return rc;
     *len = rec.size() / (size_t)c->NW;
-    for (size_t q = 0; q < *len && q < cap; ++q) decode_state(c, rec.data() + q * c->NW, &states[q]);
+    for (size_t q = 0; q < *len && q < cap; ++q) decode_state(c->sh.S, c->sh.K, rec.data() + q * c->NW, &states[q]);
     return 0;
 }
 
@@ -1571,37 +717,28 @@ int rmc_probe_bench(int device, uint64_t table_bytes, uint64_t accesses, int mod
     if (hipSetDevice(device) != hipSuccess) return RMC_E_NOGPU;
     u64 slots = 1;
     while (slots * 2 * 8 <= table_bytes) slots <<= 1;
-    u64* table = nullptr;
-    u64* sink = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
+    DevScratch<u64> table, sink;
     const u64 threads = 256ull * 2048;                       // 8 blocks of 256 per CU
     const u32 iters = (u32)std::max<u64>(1, accesses / (threads * 8));
     float ms = 0.f;
-    if (hipMalloc(&table, slots * 8) != hipSuccess || hipMalloc(&sink, 8) != hipSuccess) { rc = RMC_E_NOMEM; goto out; }
-    if (hipStreamCreate(&st) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        rc = RMC_E_HIP;
-        goto out;
-    }
-    if (hipMemsetAsync(table, 0, slots * 8, st) != hipSuccess) { rc = RMC_E_HIP; goto out; }
-    // warm-up launch (page mapping, clocks), then the timed one
-    if (launch_probe_bench(table, slots - 1, threads, 1, mode, sink, st) != hipSuccess) { rc = RMC_E_HIP; goto out; }
-    if (hipEventRecord(e0, st) != hipSuccess) { rc = RMC_E_HIP; goto out; }
-    if (launch_probe_bench(table, slots - 1, threads, iters, mode, sink, st) != hipSuccess) { rc = RMC_E_HIP; goto out; }
-    if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-        hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-        rc = RMC_E_HIP;
-        goto out;
-    }
-    *per_second = (double)threads * 8.0 * iters / (1e-3 * ms);
-out:
+    if (table.alloc(slots) != hipSuccess || sink.alloc(1) != hipSuccess) return RMC_E_NOMEM;
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool ok =
+        hipStreamCreate(&st) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+        hipMemsetAsync(table.get(), 0, slots * 8, st) == hipSuccess &&
+        // warm-up launch (page mapping, clocks), then the timed one
+        launch_probe_bench(table.get(), slots - 1, threads, 1, mode, sink.get(), st) == hipSuccess &&
+        hipEventRecord(e0, st) == hipSuccess &&
+        launch_probe_bench(table.get(), slots - 1, threads, iters, mode, sink.get(), st) == hipSuccess &&
+        hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+        hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);
-    (void)hipFree(table);
-    (void)hipFree(sink);
-    return rc;
+    if (!ok) return RMC_E_HIP;
+    *per_second = (double)threads * 8.0 * iters / (1e-3 * ms);
+    return 0;
 }
 
 int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view* out, size_t cap, size_t* n_out) {
@@ -1614,27 +751,24 @@ int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view
     std::vector<u32> packed(n * (size_t)NW);
     std::string why;
     for (size_t t = 0; t < n; ++t)
-        if (encode_view(c, states[t], packed.data() + t * NW, &why))
+        if (encode_view(c->sh.S, c->sh.K, states[t], packed.data() + t * NW, &why))
             return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
     const u64 lanes = (u64)c->P.off[10];
     const u64 rcap = std::max<u64>(1, std::min<u64>((u64)cap, n * lanes));
-    u32 *d_in = nullptr, *d_out = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    HIPCHK(c, hipMalloc(&d_in, packed.size() * 4));
-    HIPCHK(c, hipMalloc(&d_out, rcap * (u64)RW * 4));
-    HIPCHK(c, hipMalloc(&d_cnt, 8));
-    HIPCHK(c, hipMemcpy(d_in, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset(d_cnt, 0, 8));
-    HIPCHK(c, launch(c->sh, Op::List, c->P, c->PT, c->B, (u64)n, 0, d_in, d_out, rcap, d_cnt, c->st));
+    DevScratch<u32> d_in, d_out;
+    DevScratch<unsigned long long> d_cnt;
+    HIPCHK(c, d_in.alloc(packed.size()));
+    HIPCHK(c, d_out.alloc(rcap * (u64)RW));
+    HIPCHK(c, d_cnt.alloc(1));
+    HIPCHK(c, hipMemcpy(d_in.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_cnt.get(), 0, 8));
+    HIPCHK(c, launch(c, Op::List, (u64)n, 0, d_in.get(), d_out.get(), rcap, d_cnt.get()));
     HIPCHK(c, hipStreamSynchronize(c->st));
     unsigned long long cnt = 0;
-    HIPCHK(c, hipMemcpy(&cnt, d_cnt, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&cnt, d_cnt.get(), 8, hipMemcpyDeviceToHost));
     const u64 got = std::min<u64>(cnt, rcap);
     std::vector<u32> recs(got * (u64)RW);
-    if (got) HIPCHK(c, hipMemcpy(recs.data(), d_out, recs.size() * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_cnt);
+    if (got) HIPCHK(c, hipMemcpy(recs.data(), d_out.get(), recs.size() * 4, hipMemcpyDeviceToHost));
     // deterministic order: (parent, lane)
     std::vector<u64> order(got);
     for (u64 q = 0; q < got; ++q) order[q] = q;
@@ -1653,7 +787,7 @@ int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view
         s.family = family_of(c->P, (int)r[2]);
         s.in_constraint = (int)r[3];
         s.fingerprint = (u64)r[4] | ((u64)r[5] << 32);
-        if (s.in_constraint) decode_state(c, r + 6, &s.state);
+        if (s.in_constraint) decode_state(c->sh.S, c->sh.K, r + 6, &s.state);
     }
     *n_out = (size_t)cnt;
     return 0;

@@ -1,15 +1,17 @@
-// rmc_ctx.h — the host-side context behind the C ABI (rmc_api.cpp, rmc_dist.cpp).
+// rmc_ctx.h — the host-side context behind the C ABI: rmc_api.cpp (create, run,
+// trace, expand, simulate), rmc_spill.cpp, rmc_ckpt.cpp, rmc_wide.cpp, rmc_dist.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/rmc.h"
-#include "raft_packed.h"
+#include "rmc_codec.h"
 #include "rmc_internal.h"
 #include "rmc_plan.h"
 
@@ -177,10 +179,6 @@ int fail(rmc_ctx* c, int code, const std::string& msg);
 int kcap_for(int max_msgs);
 int validate(const rmc_config* c, std::string* why);
 void fill_params(rmc_ctx* c);
-int family_of(const rmc::Params& P, int lane);
-int encode_view(const rmc_ctx* c, const rmc_state_view& v, rmc::u32* out, std::string* why);
-void decode_state(const rmc_ctx* c, const rmc::u32* in, rmc_state_view* v);
-void init_view(const rmc_config& g, rmc_state_view* v);
 int reset_counters(rmc_ctx* c, bool keep_count);
 int read_counters(rmc_ctx* c);
 // After the seed launch's read_counters, on either layout: level 1 is the states
@@ -210,11 +208,16 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user);
 int trace_sharded(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
                   size_t* len);
 void free_dist(rmc_ctx* c);
-// frontier spill (rmc_api.cpp)
+// frontier spill (rmc_spill.cpp)
+rmc::u64 max_new_per_state(const rmc_ctx* c);  // what the window's launches are sized by
 void spill_rebase(rmc_ctx* c, rmc::u64 base);
 int spill_reserve(rmc_ctx* c);
+void spill_prefault_ahead(rmc_ctx* c, rmc::u64 f1);  // back the link pages [faulted, f1) on X.ahead
 int spill_to(rmc_ctx* c, rmc::u64 a, rmc::u64 count);
 void spill_free(rmc_ctx* c);
+int verify_spill_reserve(rmc_ctx* c);
+int verify_copy_out(rmc_ctx* c, rmc::u64 upto);
+int verify_host_hits(rmc_ctx* c, rmc::u64 n);
 int read_link(rmc_ctx* c, rmc::u64 idx, rmc::u64* parent, uint8_t* act);
 // the wide layout (rmc_wide.cpp)
 bool wide_wanted(const rmc_config& g);
@@ -228,5 +231,88 @@ int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_vie
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, rmc::i64 rec_beh,
              std::vector<rmc_state_view>* rec);
 void fill_wide_model(rmc_ctx* c);
-int smoke_views(const rmc_ctx* c, const rmc_sim_config& sc, std::vector<rmc_state_view>* views, std::string* why);
+inline SmokeShape smoke_shape(const rmc_config& g, bool wide) {  // what SmokeInit draws for (rmc_codec.h)
+    return {g.n_servers, g.n_values, wide, wide ? rmc::wide::KW : kcap_for(g.max_msgs)};
+}
+
+// A kernel of this ctx's shape and model (rmc_internal.h launch): on c->B and the
+// ctx stream, or on other buffers / another stream.
+inline hipError_t launch_on(rmc_ctx* c, const rmc::DevBufs& B, hipStream_t st, rmc::Op op, rmc::u64 a = 0,
+                            rmc::u64 b = 0, const rmc::u32* in = nullptr, rmc::u32* out = nullptr, rmc::u64 cap = 0,
+                            unsigned long long* count = nullptr) {
+    return rmc::launch(c->sh, op, c->P, c->PT, B, a, b, in, out, cap, count, st);
+}
+inline hipError_t launch(rmc_ctx* c, rmc::Op op, rmc::u64 a = 0, rmc::u64 b = 0, const rmc::u32* in = nullptr,
+                         rmc::u32* out = nullptr, rmc::u64 cap = 0, unsigned long long* count = nullptr) {
+    return launch_on(c, c->B, c->st, op, a, b, in, out, cap, count);
+}
+
+// A per-call allocation of n T's (hipMalloc; Pinned: hipHostMalloc), freed at scope exit.
+template <class T, bool Pinned = false>
+class DevScratch {
+    void* p_ = nullptr;
+
+public:
+    DevScratch() = default;
+    DevScratch(DevScratch&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    ~DevScratch() { (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); }  // (a null pointer is no error)
+    hipError_t alloc(size_t n) {  // once per object
+        return Pinned ? hipHostMalloc(&p_, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p_, n * sizeof(T));
+    }
+    T* get() const { return (T*)p_; }
+};
+
+// Simulation, both layouts: the counters start clear, `go` launches the walks on
+// c->st between ev0 and ev1, and *h is what they counted.
+template <class F>
+int sim_timed(rmc_ctx* c, rmc::SimCounters* d_out, rmc::SimCounters* h, float* ms, F go) {
+    *h = rmc::SimCounters{};
+    h->viol = ~0ull;
+    HIPCHK(c, hipMemcpy(d_out, h, sizeof *h, hipMemcpyHostToDevice));
+    HIPCHK(c, hipEventRecord(c->ev0, c->st));
+    HIPCHK(c, go());
+    HIPCHK(c, hipEventRecord(c->ev1, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    HIPCHK(c, hipMemcpy(h, d_out, sizeof *h, hipMemcpyDeviceToHost));
+    return 0;
+}
+inline void fill_sim_result(rmc_sim_result* out, const rmc::SimCounters& h, rmc::u64 behaviours, rmc::u64 n_init,
+                            float ms, std::chrono::steady_clock::time_point t0) {
+    memset(out, 0, sizeof *out);
+    out->behaviours = behaviours;
+    out->steps = h.steps;
+    out->init_states = n_init;
+    out->truncated = h.truncated;
+    out->deadlocked = h.deadlocked;
+    if (h.viol != ~0ull) {
+        out->violated_inv = 1 << (int)((h.viol >> 40) & 15);
+        out->violation_depth = (int32_t)(h.viol >> 44);
+        out->violation_behaviour = h.viol & ((1ull << 40) - 1);
+    }
+    out->kernel_seconds = 1e-3 * ms;
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The counterexample's parent links from the target back to an initial state, then
+// reversed: read_one(idx, &parent, &act) reads one link.
+template <class F>
+int walk_links(rmc_ctx* c, F read_one, std::vector<rmc::u64>* chain, std::vector<uint8_t>* acts) {
+    for (rmc::u64 idx = c->target_idx;;) {
+        rmc::u64 p = 0;
+        uint8_t a = 0;
+        if (int rc = read_one(idx, &p, &a)) return rc;
+        chain->push_back(idx);
+        acts->push_back(a);
+        if (p == ~0ull || chain->size() > 100000) break;
+        idx = p;
+    }
+    std::reverse(chain->begin(), chain->end());
+    std::reverse(acts->begin(), acts->end());
+    return 0;
+}
+inline void fill_step(int32_t* families, int32_t* instances, size_t q, int family, uint8_t act) {
+    if (families) families[q] = family;
+    if (instances) instances[q] = act == 255 ? -1 : act;
+}
 }  // namespace rmc_host

@@ -451,9 +451,9 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         init_view(c->cfg, &iv);
         std::vector<u32> packed((size_t)c->NW);
         std::string why;
-        if (encode_view(c, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
+        if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
         HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(c, launch(c->sh, Op::Seed, c->P, c->PT, c->B, 1, 0, c->d_staged, nullptr, 0, nullptr, c->st));
+        HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
     }
     std::vector<Counters> rows((size_t)W);
     // level end: the all-gathered device counters; errors stop every rank alike
@@ -488,7 +488,7 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         c->level_start.push_back(c->h_ctr->count);
     }
     if (verify && !resume && c->h_ctr->count)  // slot -> store index of the initial state(s)
-        HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, 0, c->h_ctr->count, nullptr, nullptr, 0, nullptr, c->st));
+        HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
     u64 total_prev = 0;
     std::vector<u64> count_before((size_t)W);  // every rank's store count when the current level began
     for (int r = 0; r < W; ++r) {
@@ -558,7 +558,7 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
             // expands all of it and keeps the successors it owns; no key or
             // state exchange, one all-gather of the level's records
             D.phase = "replicated level (frontier all-gather)";
-            if (hi > lo) HIPCHK(c, launch(c->sh, Op::PackRep, c->P, c->PT, c->B, lo, hi, nullptr, D.rep_send, 0, nullptr, c->st));
+            if (hi > lo) HIPCHK(c, launch(c, Op::PackRep, lo, hi, nullptr, D.rep_send));
             HIPCHK(c, hipEventRecord(D.ev_c, c->st));
             HIPCHK(c, hipStreamWaitEvent(D.xs, D.ev_c, 0));
             if (int rc = gather_level(c, fsz, RBR)) return rc;
@@ -569,7 +569,7 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
             Bb.rep = D.rep_buf;
             // one launch (rep_max <= 2^24 records); timed by events read after the level end
             HIPCHK(c, hipEventRecord(D.set[0].k0, c->st));
-            HIPCHK(c, launch(c->sh, Op::ExpandRep, c->P, c->PT, Bb, 0, ftot, nullptr, nullptr, 0, nullptr, c->st));
+            HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandRep, 0, ftot));
             HIPCHK(c, hipEventRecord(D.set[0].k1, c->st));
             rep_timed = ftot != 0;
             c->res.expand_launches += 1;
@@ -611,10 +611,10 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 const u64 rest = hi - cursor, nr = (rest + cap - 1) / cap;
                 const u64 n = (rest + nr - 1) / nr;
                 HIPCHK(c, hipEventRecord(S.k0, c->st));
-                HIPCHK(c, launch(c->sh, Op::ExpandDist, c->P, c->PT, Bb, cursor, cursor + n, nullptr, nullptr, 0, nullptr, c->st));
+                HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandDist, cursor, cursor + n));
                 // the pool flush's remote successors: keyed and routed to the outboxes
                 if (W > 1 && !verify && !c->sh.sym)
-                    HIPCHK(c, launch(c->sh, Op::Route, c->P, c->PT, Bb, 0, 0, nullptr, nullptr, 0, nullptr, c->st));
+                    HIPCHK(c, launch_on(c, Bb, c->st, Op::Route));
                 HIPCHK(c, hipEventRecord(S.k1, c->st));
                 S.timed = 1;
                 c->res.expand_launches += 1;
@@ -626,10 +626,10 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 if (int rc = read_counters(c)) return rc;
                 const u64 c1 = c->h_ctr->count;
                 if (c1 > vpub)
-                    HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, vpub, c1, nullptr, nullptr, 0, nullptr, c->st));
+                    HIPCHK(c, launch(c, Op::Publish, vpub, c1));
                 vpub = c1;
                 if (c->h_ctr->vcount) {
-                    HIPCHK(c, launch(c->sh, Op::Verify, c->P, c->PT, c->B, c->h_ctr->vcount, 0, nullptr, nullptr, 0, nullptr, c->st));
+                    HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
                     HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
                 }
             }
@@ -769,8 +769,7 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 Bb.tick_out = S.tick_out;
                 Bb.ocount = S.ocount;
                 Bb.pool = S.pool;  // tickets POOL_TICK | index name this set's pool records
-                HIPCHK(c, launch(c->sh, Op::MaterializeRemote, c->P, c->PT, Bb, mx, 0, reinterpret_cast<const u32*>(D.rep_in), nullptr, 0,
-                                 nullptr, D.xs));
+                HIPCHK(c, launch_on(c, Bb, D.xs, Op::MaterializeRemote, mx, 0, reinterpret_cast<const u32*>(D.rep_in)));
             }
             HIPCHK(c, hipEventRecord(S.ev_free, D.xs));  // the set's keys and tickets are consumed
             HIPCHK(c, hipMemcpyAsync(D.h_sa, D.sa, 16 * (u64)W, hipMemcpyDeviceToHost, D.xs));
@@ -793,16 +792,16 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
             if (tot_st > (u64)W * kcap) return fail(c, RMC_E_CAPACITY, "phase-2 inbox full at " + where(c));
             if (int rc = a2a(c, c->B.st_out, soff.data(), scnt.data(), D.st_in, roff.data(), rcnt.data())) return rc;
             if (tot_st)
-                HIPCHK(c, launch(c->sh, Op::StoreRemote, c->P, c->PT, c->B, tot_st, 0, D.st_in, nullptr, 0, nullptr, D.xs));
+                HIPCHK(c, launch_on(c, c->B, D.xs, Op::StoreRemote, tot_st, 0, D.st_in));
             if (verify && tot_st) {  // publish the received new states, then compare the seen ones
                 HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
                 if (int rc = xwait(c, D.ev_h)) return rc;
                 if (int rc = read_counters(c)) return rc;
                 const u64 c2 = c->h_ctr->count;
                 if (c2 > vpub)
-                    HIPCHK(c, launch(c->sh, Op::Publish, c->P, c->PT, c->B, vpub, c2, nullptr, nullptr, 0, nullptr, D.xs));
+                    HIPCHK(c, launch_on(c, c->B, D.xs, Op::Publish, vpub, c2));
                 vpub = c2;
-                HIPCHK(c, launch(c->sh, Op::CompareRemote, c->P, c->PT, c->B, tot_st, 0, D.st_in, nullptr, 0, nullptr, D.xs));
+                HIPCHK(c, launch_on(c, c->B, D.xs, Op::CompareRemote, tot_st, 0, D.st_in));
                 HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
                 if (int rc = xwait(c, D.ev_h)) return rc;
             }
@@ -938,9 +937,8 @@ int trace_sharded(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t
     std::reverse(chain_act.begin(), chain_act.end());
     *len = chain_states.size();
     for (size_t q = 0; q < chain_states.size() && q < cap; ++q) {
-        if (states) decode_state(c, chain_states[q].data(), &states[q]);
-        if (families) families[q] = family_of(c->P, chain_act[q]);
-        if (instances) instances[q] = chain_act[q] == 255 ? -1 : chain_act[q];
+        if (states) decode_state(c->sh.S, c->sh.K, chain_states[q].data(), &states[q]);
+        fill_step(families, instances, q, family_of(c->P, chain_act[q]), chain_act[q]);
     }
     return 0;
 }

@@ -5,13 +5,18 @@ Pinned by: the SmokeInit initial-state counts k^9 (Smokeraft.tla:18: 1, 512,
 (Smokeraft.tla:11-15, 24-76), and every step of replayed behaviours being a
 successor under the Python restatement of Next.  Which successor TLC's
 simulator picks is random, so parity with TLC is distributional only."""
+import ctypes as C
+import hashlib
+import json
+import os
+
 import pytest
 
 import rmc
 from oracle import raft_spec as R
 from tests.convert import from_view
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu  # every test but the SmokeInit digests needs the device
 
 
 def smoke_cfg(**kw):
@@ -20,12 +25,34 @@ def smoke_cfg(**kw):
                            state_capacity=1 << 12, **kw)
 
 
+@gpu
 @pytest.mark.parametrize("k,n", [(1, 1), (2, 512), (3, 19683)])
 def test_smokeinit_counts(k, n):
     with rmc.Checker(smoke_cfg()) as ck:
         r = ck.simulate(behaviours=1024, depth=1, smoke_k=k, seed=7)
     assert r.init_states == n
     assert r.steps == 0 and r.violated_inv == 0
+
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "smokeinit_digests.json")) as _f:
+    SMOKE_DIGESTS = json.load(_f)
+
+
+@pytest.mark.parametrize("layout", ["packed", "wide"])
+@pytest.mark.parametrize("k,nat,seed", [(1, 2, 1), (2, 2, 7), (3, 3, 11)])
+def test_smokeinit_draws_are_pinned(layout, k, nat, seed):
+    """The views rmc_smoke_init returns (host only, no device) are byte for byte
+    those of the commit named in tests/golden/smokeinit_digests.json: the
+    sampler's std::mt19937_64 draws, their order, and — on the packed layout —
+    the encode / decode round trip of every view."""
+    cfg = smoke_cfg() if layout == "packed" else rmc.make_config(
+        n_servers=3, n_values=2, max_term=14, max_log_len=4, max_msgs=8, max_dup=3)
+    sc = rmc.SimConfig(1, 100, k, nat, 0, seed)
+    st = (rmc.StateView * k ** 9)()
+    n = C.c_size_t()
+    assert rmc.native().rmc_smoke_init(C.byref(cfg), C.byref(sc), st, len(st), C.byref(n)) == 0
+    assert n.value == k ** 9
+    assert hashlib.sha256(st).hexdigest() == SMOKE_DIGESTS[f"{layout}:{k}:{nat}:{seed}"]
 
 
 def in_smoke_domains(s, nat=2):
@@ -45,6 +72,7 @@ def in_smoke_domains(s, nat=2):
     return ok
 
 
+@gpu
 def test_replayed_behaviours_are_behaviours_of_the_spec():
     model = R.Model()  # no CONSTRAINT in simulation
     with rmc.Checker(smoke_cfg()) as ck:
@@ -58,6 +86,7 @@ def test_replayed_behaviours_are_behaviours_of_the_spec():
             assert all(R.type_ok(model, s) for s in states)
 
 
+@gpu
 def test_simulation_runs_at_scale():
     """Default mode: draws among the successors within the packed capacity, so
     behaviours run to depth 100 (TLC -simulate's default depth)."""
@@ -69,6 +98,7 @@ def test_simulation_runs_at_scale():
     assert r.steps + 100 * r.deadlocked >= (1 << 18) * 99
 
 
+@gpu
 def test_simulation_truncate_mode_counts_capacity_exits():
     """RMC_SIM_TRUNCATE draws among all enabled successors (TLC's distribution
     while the state fits) and ends a behaviour whose draw exceeds the packed
@@ -81,6 +111,7 @@ def test_simulation_truncate_mode_counts_capacity_exits():
     assert r.truncated + r.deadlocked <= 1 << 16
 
 
+@gpu
 def test_simulation_finds_the_injected_bug():
     """Config 5's bug (BecomeLeader with votesGranted /= {}) is found by random
     simulation from Init too; the reported state index is a real violation."""

@@ -118,16 +118,67 @@ int read_counters(rmc_ctx* c) {
     return 0;
 }
 
+int begin_set(rmc_ctx* c, bool tagged) {
+    const char* epe = getenv("RMC_SET_EPOCH");  // (read per run: tests vary it)
+    const u32 ep_max = epe ? (u32)std::min(255, std::max(0, atoi(epe))) : 255u;
+    const SetEpoch e = next_set_epoch(c->set_epoch, ep_max, tagged);
+    if (e.clear) HIPCHK(c, launch_fill(c->B.table, c->table_slots * 8, 0, c->st));
+    c->set_epoch = e.epoch;
+    if (c->sh.verify) HIPCHK(c, launch_fill(c->B.sidx, c->table_slots * 8, 0xFF, c->st));
+    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+    return 0;
+}
+
+int seed_init(rmc_ctx* c) {
+    rmc_state_view iv;
+    init_view(c->cfg, &iv);
+    std::vector<u32> packed((size_t)c->NW);
+    std::string why;
+    if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
+    HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
+    return 0;
+}
+
+int level_error(rmc_ctx* c, const Counters& k, int depth, const LevelText& text, int rank) {
+    const std::string on = rank < 0 ? "" : " on rank " + std::to_string(rank);
+    if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full" + on);
+    if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, depth));
+    if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full" + on);
+    if (text.tie_full && (k.overflow & 16u)) return fail(c, RMC_E_CAPACITY, text.tie_full);
+    if (k.overflow & 8u) return fail(c, RMC_E_HIP, text.no_owner + on);
+    if (rank >= 0 && (k.overflow & 2u))
+        return fail(c, RMC_E_CAPACITY, "exchange parking buffer full" + on + " (raise keys_per_dest)");
+    if (k.overflow && rank >= 0)
+        return fail(c, RMC_E_CAPACITY, "state store full" + on + " (raise rmc_config.state_capacity)");
+    if (k.overflow)
+        return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(c->B.cap) + " " + text.store_noun +
+                                           "); raise rmc_config.state_capacity");
+    return 0;
+}
+
+void scan_target(rmc_ctx* c, const Counters* rows, int n, int depth) {
+    for (int r = 0; r < n && !c->have_target; ++r)  // the lowest rank's least violating index
+        if (rows[r].viol != ~0ull) {
+            c->res.violated_inv = 1 << (int)(rows[r].viol & 15);
+            c->res.violation_depth = depth;
+            c->have_target = 1;
+            c->target_idx = ((u64)r << 48) | (rows[r].viol >> 4);
+        }
+    if (c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK)
+        for (int r = 0; r < n && !c->have_target; ++r)
+            if (rows[r].deadlock != ~0ull) {
+                c->res.deadlock = 1;
+                c->have_target = 1;
+                c->target_idx = ((u64)r << 48) | rows[r].deadlock;
+            }
+}
+
 int seed_done(rmc_ctx* c) {
     c->res.generated = 1;
     c->level_start.push_back(0);
     c->level_start.push_back(c->h_ctr->count);
-    if (c->h_ctr->viol != ~0ull) {
-        c->res.violated_inv = 1 << (int)(c->h_ctr->viol & 15);
-        c->res.violation_depth = 1;
-        c->have_target = 1;
-        c->target_idx = c->h_ctr->viol >> 4;
-    }
+    scan_target(c, c->h_ctr, 1, 1);  // (a seed launch finds no deadlock: Counters.deadlock stays ~0)
     return c->h_ctr->count ? 1 : 0;
 }
 
@@ -140,16 +191,9 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     c->res.expand_kernel_seconds += 1e-3 * ms;
     const Counters& k = *c->h_ctr;
-    if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full");
-    if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, *depth));
-    if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full");
-    if (text.tie_full && (k.overflow & 16u)) return fail(c, RMC_E_CAPACITY, text.tie_full);
-    if (k.overflow & 8u) return fail(c, RMC_E_HIP, text.no_owner);
+    if (int rc = level_error(c, k, *depth, text, -1)) return rc;
     c->res.collisions += k.collisions;
     c->res.verified += k.vchecked;
-    if (k.overflow)
-        return fail(c, RMC_E_CAPACITY, "state store full (capacity " + std::to_string(c->B.cap) + " " + text.store_noun +
-                                           "); raise rmc_config.state_capacity");
     c->res.generated += k.generated;
     c->res.probes += k.probes;
     if (text.walked) *text.walked += k.walked;
@@ -159,16 +203,7 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
         c->level_start.push_back(k.count);
     }
     c->res.distinct = k.count;
-    if (k.viol != ~0ull) {
-        c->res.violated_inv = 1 << (int)(k.viol & 15);
-        c->res.violation_depth = *depth;
-        c->have_target = 1;
-        c->target_idx = k.viol >> 4;
-    } else if ((c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK) && k.deadlock != ~0ull) {
-        c->res.deadlock = 1;
-        c->have_target = 1;
-        c->target_idx = k.deadlock;
-    }
+    scan_target(c, &k, 1, *depth);
     if (cb) {
         rmc_level_stats ls{};
         ls.level = nnew ? *depth - 1 : *depth;
@@ -370,35 +405,15 @@ static int start_run(rmc_ctx* c, int* depth) {
         SpillState& X = c->spill;  // back the first spill's pages meanwhile
         if (!X.dev_links && !X.ahead.joinable()) spill_prefault_ahead(c, std::min(X.total_cap, X.win));
     }
-    // The set epoch (raft_packed.h c_set_ep): a run on a ctx whose set holds the
-    // tagged entries of an earlier run takes the next epoch and clears nothing —
-    // their slots read as empty.  The first run of a ctx, every 255th and runs
-    // with verification (whose slot -> state map is cleared anyway) clear the set
-    // (RMC_SET_EPOCH=0: every run clears; =N: at most N epochs between clears).
-    const char* epe = getenv("RMC_SET_EPOCH");  // (read per run: tests vary it)
-    const u32 ep_max = epe ? (u32)std::min(255, std::max(0, atoi(epe))) : 255u;
-    const bool tagged = ep_max > 0 && !c->sh.verify;
-    if (tagged && c->set_epoch >= 1 && c->set_epoch < ep_max) {
-        c->set_epoch += 1;
-    } else {
-        HIPCHK(c, launch_fill(c->B.table, c->table_slots * 8, 0, c->st));
-        c->set_epoch = tagged ? 1 : 0;
-    }
-    if (c->sh.verify) HIPCHK(c, launch_fill(c->B.sidx, c->table_slots * 8, 0xFF, c->st));
-    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+    // the set epoch: the next one, or a cleared set (rmc_plan.h next_set_epoch)
+    if (int rc = begin_set(c, !c->sh.verify)) return rc;
     if (int rc = reset_counters(c, false)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
 
     // ---- Init (raft.tla:125-129): one initial state
-    rmc_state_view iv;
-    init_view(c->cfg, &iv);
-    std::vector<u32> packed((size_t)c->NW);
-    std::string why;
-    if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
-    HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
+    if (int rc = seed_init(c)) return rc;
     if (int rc = read_counters(c)) return rc;
     *depth = seed_done(c);
     if (c->sh.verify) HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));

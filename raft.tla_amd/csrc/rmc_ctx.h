@@ -1,5 +1,6 @@
 // rmc_ctx.h — the host-side context behind the C ABI: rmc_api.cpp (create, run,
-// trace, expand, simulate), rmc_spill.cpp, rmc_ckpt.cpp, rmc_wide.cpp, rmc_dist.cpp.
+// trace, expand, simulate), rmc_spill.cpp, rmc_ckpt.cpp, rmc_wide.cpp, rmc_dist.cpp,
+// rmc_dist_comm.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -181,6 +182,12 @@ int validate(const rmc_config* c, std::string* why);
 void fill_params(rmc_ctx* c);
 int reset_counters(rmc_ctx* c, bool keep_count);
 int read_counters(rmc_ctx* c);
+// The set of a fresh run, single-GPU or sharded: the next set epoch or a cleared
+// set (rmc_plan.h next_set_epoch under RMC_SET_EPOCH; tagged: the run's kernels
+// can tell epochs apart), verification's slot -> state map cleared, the salt set.
+int begin_set(rmc_ctx* c, bool tagged);
+// Init (raft.tla:125-129), the one initial state: encoded, staged and seeded (k_seed).
+int seed_init(rmc_ctx* c);
 // After the seed launch's read_counters, on either layout: level 1 is the states
 // it stored, and an invariant Init violates is the target.  Returns the depth.
 int seed_done(rmc_ctx* c);
@@ -191,6 +198,14 @@ struct LevelText {
     const char* store_noun;  // "state store full (capacity N <noun>)"
     rmc::u64* walked;        // accumulates Counters.walked (nullptr: not counted)
 };
+// The error a level's counters report (Counters.table_full / overflow), 0 if
+// none; rank: the sharded rank the row came from, named in the message (-1: a
+// single GPU).  Bit 16 is the single-GPU tie buffer's, bit 2 the sharded parking buffer's.
+int level_error(rmc_ctx* c, const rmc::Counters& k, int depth, const LevelText& text, int rank);
+// The violation, else deadlock (RMC_FLAG_CHECK_DEADLOCK), the counter rows of n
+// ranks report, as the target to trace (target_idx = rank << 48 | index; the
+// lowest rank's wins); nothing if a target is already known.
+void scan_target(rmc_ctx* c, const rmc::Counters* rows, int n, int depth);
 // The end of a level's launches (hi: the states before it), from the closing
 // event to the progress callback: kernel time, the Counters.overflow errors,
 // the result's totals, level_start / depth, the violation or deadlock target.

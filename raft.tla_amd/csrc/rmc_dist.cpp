@@ -1,38 +1,43 @@
 // rmc_dist.cpp — sharded BFS over several GPUs behind the C ABI (rmc_shard).
 //
 // One ctx per GPU, each a rank of a state-space partition (SURVEY.md §8e;
-// replaces TLC's distributed mode).  Per BFS level every rank expands the
-// frontier it owns in ROUNDS; a round's exchange is two-phase, fingerprint
-// first:
-//   phase 1  k_expand<DIST> puts the key of every successor owned elsewhere
-//            (and not in the sent-cache) in that owner's key outbox with a
-//            local ticket (parent, lane); a count all-to-all tells every rank
-//            what it receives; keys all-to-all; the owner inserts them
-//            (k_owner_insert), answers new/seen with 1 byte per key and
-//            counts per source the states it will receive; replies
-//            all-to-all (the reverse of the key exchange);
-//   phase 2  k_materialize_remote re-derives the accepted successors from
-//            their tickets into per-owner state outboxes (counting them);
-//            states all-to-all; the owner stores them (k_store_remote).
+// replaces TLC's distributed mode).  A small level is REPLICATED: every rank
+// gathers the whole frontier, expands it and keeps the successors it owns.
+// Any other level every rank expands the frontier it owns in ROUNDS; a round's
+// exchange is two-phase, fingerprint first:
+//   expansion  k_expand_dist stores the new successors this rank owns and puts
+//            every new one owned elsewhere, materialised once as its phase-2
+//            record, in the round's pool (the pool flush; a send marker in the
+//            fingerprint set keeps a successor from being pooled twice);
+//            k_route keys the pool's records and fills the owners' key
+//            outboxes with tickets naming them.  (SYMMETRY and verification:
+//            k_expand<DIST> fills the outboxes itself with tickets (parent,
+//            lane), SYMMETRY behind a lossy sent-cache.)
+//   count row  a count all-to-all tells every rank what it receives;
+//   phase 1  keys all-to-all; the owner inserts them (k_owner_insert), answers
+//            new/seen with 1 byte per key and counts per source the states it
+//            will receive; replies all-to-all (the reverse of the key exchange);
+//   phase 2  k_materialize_remote copies the accepted successors' pool records
+//            (or re-derives them from their tickets) into per-owner state
+//            outboxes, counting them; states all-to-all; the owner stores them
+//            (k_store_remote).
+// The arithmetic of a round — the count row's layout, the byte blocks of the
+// three all-to-alls, the round's size — is rmc_dist_plan.h (host-tested); the
+// collectives and the deadlines on them are rmc_dist_comm.cpp.
 // Pipelining: two outbox sets.  The ctx stream expands round k + 1 into one
 // set while the exchange stream (xs) runs round k's exchange on the other, so
 // the host's two count read-backs per round wait while the GPU expands.  A
 // level ends with one all-gather of the device counters.  Keys that do not
 // fit an outbox are parked (B.ovf) and sent in later rounds of the same level:
 // an outbox overflow costs a round, never the run.
-// Collectives run on RCCL over xGMI (one communicator per ctx) or on a
-// caller-supplied host transport (gloo in the tests, where several ranks share
-// one GPU; every collective is then a synchronous host round trip).
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <memory>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
 
-#include "rmc_ctx.h"
+#include "rmc_dist_comm.h"
+#include "rmc_dist_plan.h"
 
 using namespace rmc;
 using namespace rmc_host;
@@ -43,299 +48,468 @@ namespace {
 // {k lo, k hi, s32} (raft_packed.h Fp, put_key; the owner derives its own
 // table value and slot).
 constexpr u64 KEYB = 12;
+static_assert(kPlanMaxWorld == kMaxWorld, "rmc_dist_plan.h sizes its per-peer arrays by kMaxWorld");
 
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// ---- deadlines ---------------------------------------------------------------------
-// Every wait of the sharded loop on other ranks has a deadline
-// (RMC_DIST_TIMEOUT_S, default 300 s): a collective that has not completed in
-// time aborts the RCCL communicator (ncclCommAbort also ends the kernels
-// waiting inside it) and fails the call on this rank, naming the level, the
-// round and the phase, instead of hanging until an outer time limit.  The
-// communicator is non-blocking (ncclConfig_t.blocking = 0), so connection
-// set-up inside a group call is polled under the same deadline.  A host
-// transport applies its own deadline inside its callbacks (rmc.h).
-std::string where(const rmc_ctx* c) {
-    const DistState& D = c->dist;
-    return "rank " + std::to_string(D.rank) + " of " + std::to_string(D.world) + ", level " +
-           std::to_string(D.lvl) + ", round " + std::to_string(D.rnd) + ", phase " + D.phase;
-}
-
-// ncclCommAbort of a communicator whose peers never connected can itself wait
-// on them (the bootstrap of an unfinished init): it runs on a helper thread,
-// waited for at most kAbortWait s; past that the call returns and the helper
-// is left to the process exit (after a deadline the caller ends the process,
-// rmc.h).  Returns whether the abort completed.
-constexpr double kAbortWait = 10.0;
-bool abort_bounded(ncclComm_t comm) {
-    auto done = std::make_shared<std::atomic<int>>(0);
-    std::thread([comm, done] {
-        (void)ncclCommAbort(comm);
-        done->store(1);
-    }).detach();
-    const double t0 = now_s();
-    while (!done->load() && now_s() - t0 < kAbortWait) std::this_thread::sleep_for(std::chrono::milliseconds(2));
-    return done->load() != 0;
-}
-
-// pending: the caller left a communicator it could not abort (communicator init).
-int deadline_fail(rmc_ctx* c, const char* what, int pending = 0) {
-    DistState& D = c->dist;
-    D.aborted = 1;
-    bool aborted = !pending;
-    if (D.rccl && D.comm) {
-        aborted = abort_bounded(D.comm);
-        D.comm = nullptr;
-    }
-    if (D.rccl) D.abort_pending = aborted ? 0 : 1;
-    char t[32];
-    snprintf(t, sizeof t, "%g", D.timeout_s);
-    return fail(c, RMC_E_HIP, std::string("sharded search: ") + what + " did not complete within the " + t +
-                                  " s deadline (RMC_DIST_TIMEOUT_S) at " + where(c) +
-                                  (!D.rccl ? "" : aborted ? "; the RCCL communicator was aborted"
-                                                          : "; the RCCL communicator's abort is still pending "
-                                                            "(end the process)"));
-}
-
-// Wait for an event of the exchange path under the deadline: spin first (a
-// round's read-back is on the critical path), then back off.
-int xwait(rmc_ctx* c, hipEvent_t ev) {
-    DistState& D = c->dist;
-    const double t0 = now_s();
-    for (u64 spin = 0;; ++spin) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady)
-            return fail(c, RMC_E_HIP, std::string("hipEventQuery: ") + hipGetErrorString(e) + " at " + where(c));
-        if ((spin & 63) == 0) {
-            const double dt = now_s() - t0;
-            if (dt > D.timeout_s) return deadline_fail(c, "a wait on the exchange");
-            // a level's expansion takes up to tens of ms: poll without sleeping for
-            // the first 100 ms (a 20-us sleep wakes 50-80 us late, once per wait),
-            // then gently (a stalled peer)
-            if (dt > 0.1) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    D.wait_seconds += now_s() - t0;
-    return 0;
-}
-
-// The result of an RCCL call on the non-blocking communicator: ncclInProgress
-// is polled (ncclCommGetAsyncError) until the call is enqueued, under the deadline.
-int nccl_done(rmc_ctx* c, ncclResult_t r, const char* what) {
-    DistState& D = c->dist;
-    if (r == ncclInProgress || (r == ncclSuccess && D.nonblocking)) {
-        const double t0 = now_s();
-        for (u64 spin = 0;; ++spin) {
-            if (!D.comm) return fail(c, RMC_E_HIP, std::string(what) + ": no communicator at " + where(c));
-            if (ncclCommGetAsyncError(D.comm, &r) != ncclSuccess) break;
-            if (r != ncclInProgress) break;
-            if ((spin & 63) == 0 && now_s() - t0 > D.timeout_s) return deadline_fail(c, what);
-            if (spin > 4096) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    if (r != ncclSuccess) return fail(c, RMC_E_HIP, std::string(what) + ": " + ncclGetErrorString(r) + " at " + where(c));
-    return 0;
-}
-
-#define NCCLCHK(c, expr)                                              \
-    do {                                                              \
-        if (int rc_ = nccl_done((c), (expr), #expr)) return rc_;      \
-    } while (0)
-
-// The host transport's callbacks return non-zero on failure, their own
-// deadline included (rmc.h): the call fails naming where; a callback that
-// failed after the deadline had passed is reported as the deadline.
-int host_fail(rmc_ctx* c, const char* what, double t0) {
-    const DistState& D = c->dist;
-    if (now_s() - t0 >= 0.9 * D.timeout_s) {
-        char t[32];
-        snprintf(t, sizeof t, "%g", D.timeout_s);
-        return fail(c, RMC_E_HIP, std::string("sharded search: the host transport's ") + what +
-                                      " did not complete within the " + t + " s deadline (RMC_DIST_TIMEOUT_S) at " +
-                                      where(c));
-    }
-    return fail(c, RMC_E_HIP, std::string("host transport ") + what + " failed at " + where(c));
-}
-
-// All-to-all of per-peer byte blocks living on the device, on the exchange
-// stream: block p of the send side is sbuf + soff[p] (scnt[p] bytes) for rank
-// p; block p of the receive side lands at rbuf + roff[p] (rcnt[p] bytes) from
-// rank p.
-int a2a(rmc_ctx* c, const void* sbuf, const u64* soff, const u64* scnt, void* rbuf, const u64* roff, const u64* rcnt) {
-    DistState& D = c->dist;
-    const int W = D.world;
-    if (D.rccl) {
-        bool any = false;
-        for (int p = 0; p < W; ++p) any |= scnt[p] || rcnt[p];
-        if (!any) return 0;
-        NCCLCHK(c, ncclGroupStart());
-        for (int p = 0; p < W; ++p) {
-            if (scnt[p]) {
-                const ncclResult_t r = ncclSend((const char*)sbuf + soff[p], scnt[p], ncclUint8, p, D.comm, D.xs);
-                if (r != ncclSuccess && r != ncclInProgress) {
-                    (void)ncclGroupEnd();
-                    return nccl_done(c, r, "ncclSend");
-                }
-            }
-            if (rcnt[p]) {
-                const ncclResult_t r = ncclRecv((char*)rbuf + roff[p], rcnt[p], ncclUint8, p, D.comm, D.xs);
-                if (r != ncclSuccess && r != ncclInProgress) {
-                    (void)ncclGroupEnd();
-                    return nccl_done(c, r, "ncclRecv");
-                }
-            }
-        }
-        NCCLCHK(c, ncclGroupEnd());
-        return 0;
-    }
-    u64 st = 0, rt = 0;
-    for (int p = 0; p < W; ++p) { st += scnt[p]; rt += rcnt[p]; }
-    D.stage_send.resize(std::max<u64>(st, 1));
-    D.stage_recv.resize(std::max<u64>(rt, 1));
-    u64 o = 0;
-    for (int p = 0; p < W; ++p) {
-        if (scnt[p])
-            HIPCHK(c, hipMemcpyAsync(D.stage_send.data() + o, (const char*)sbuf + soff[p], scnt[p], hipMemcpyDeviceToHost,
-                                     D.xs));
-        o += scnt[p];
-    }
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    if (int rc = xwait(c, D.ev_h)) return rc;
-    const double th = now_s();
-    if (D.host.alltoallv(D.host.user, D.stage_send.data(), scnt, D.stage_recv.data(), rcnt))
-        return host_fail(c, "alltoallv", th);
-    o = 0;
-    for (int p = 0; p < W; ++p) {
-        if (rcnt[p])
-            HIPCHK(c, hipMemcpyAsync((char*)rbuf + roff[p], D.stage_recv.data() + o, rcnt[p], hipMemcpyHostToDevice, D.xs));
-        o += rcnt[p];
-    }
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    return xwait(c, D.ev_h);
-}
-
-// All-to-all of `per` u64 per peer between device buffers (the count rows).
-int a2a_u64(rmc_ctx* c, const u64* send, u64* recv, u64 per) {
-    DistState& D = c->dist;
-    if (D.world == 1) {  // a world of one: the row to itself, no collective
-        HIPCHK(c, hipMemcpyAsync(recv, send, per * 8, hipMemcpyDeviceToDevice, D.xs));
-        return 0;
-    }
-    if (D.rccl) {
-        NCCLCHK(c, ncclAllToAll(send, recv, per, ncclUint64, D.comm, D.xs));
-        return 0;
-    }
-    std::vector<u64> off((size_t)D.world), cnt((size_t)D.world, per * 8);
-    for (int p = 0; p < D.world; ++p) off[(size_t)p] = (u64)p * per * 8;
-    return a2a(c, send, off.data(), cnt.data(), recv, off.data(), cnt.data());
-}
-
-// All-gather of `bytes` host bytes per rank into all (world * bytes, rank order).
-int allgather(rmc_ctx* c, const void* mine, u64 bytes, void* all) {
-    DistState& D = c->dist;
-    if (!D.rccl) {
-        const double th = now_s();
-        if (D.host.allgather(D.host.user, mine, bytes, all)) return host_fail(c, "allgather", th);
-        return 0;
-    }
-    const bool big = bytes > D.ag_cap;  // rows are small: the staging buffer is allocated once
-    void* d_buf = D.ag_dev;
-    if (big) HIPCHK(c, hipMallocAsync(&d_buf, bytes * (u64)(D.world + 1), D.xs));
-    char* d_in = (char*)d_buf + bytes * (u64)D.world;
-    HIPCHK(c, hipMemcpyAsync(d_in, mine, bytes, hipMemcpyHostToDevice, D.xs));
-    NCCLCHK(c, ncclAllGather(d_in, d_buf, bytes, ncclUint8, D.comm, D.xs));
-    HIPCHK(c, hipMemcpyAsync(all, d_buf, bytes * (u64)D.world, hipMemcpyDeviceToHost, D.xs));
-    if (big) HIPCHK(c, hipFreeAsync(d_buf, D.xs));
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    return xwait(c, D.ev_h);
-}
-
-// All-gather of this rank's device counters (the level statistics), after
-// every kernel of the level on both streams.
-int allgather_counters(rmc_ctx* c, Counters* rows) {
-    DistState& D = c->dist;
-    HIPCHK(c, hipEventRecord(D.ev_c, c->st));
-    HIPCHK(c, hipStreamWaitEvent(D.xs, D.ev_c, 0));
-    const u64 bytes = sizeof(Counters);
-    if (D.rccl) {
-        NCCLCHK(c, ncclAllGather(c->B.ctr, D.ag_dev, bytes, ncclUint8, D.comm, D.xs));
-        HIPCHK(c, hipMemcpyAsync(rows, D.ag_dev, bytes * (u64)D.world, hipMemcpyDeviceToHost, D.xs));
-        HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-        return xwait(c, D.ev_h);
-    }
-    Counters mine;
-    HIPCHK(c, hipMemcpyAsync(&mine, c->B.ctr, bytes, hipMemcpyDeviceToHost, D.xs));
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    if (int rc = xwait(c, D.ev_h)) return rc;
-    const double th = now_s();
-    if (D.host.allgather(D.host.user, &mine, bytes, rows)) return host_fail(c, "allgather", th);
-    return 0;
-}
-
-// Replicated level: every rank's records (n[p] of them, rb bytes each) into
-// D.rep_buf, contiguous in rank order; this rank's own block is copied locally.
-int gather_level(rmc_ctx* c, const std::vector<u64>& n, u64 rb) {
-    DistState& D = c->dist;
-    const int W = D.world, me = D.rank;
-    std::vector<u64> off((size_t)W + 1, 0);
-    for (int p = 0; p < W; ++p) off[(size_t)p + 1] = off[(size_t)p] + n[(size_t)p];
-    char* dst = (char*)D.rep_buf;
-    if (n[(size_t)me])
-        HIPCHK(c, hipMemcpyAsync(dst + off[(size_t)me] * rb, D.rep_send, n[(size_t)me] * rb, hipMemcpyDeviceToDevice,
-                                 D.xs));
-    if (W == 1) return 0;
-    if (D.rccl) {
-        bool any = false;
-        for (int p = 0; p < W; ++p) any |= p != me && (n[(size_t)p] || n[(size_t)me]);
-        if (!any) return 0;
-        NCCLCHK(c, ncclGroupStart());
-        for (int p = 0; p < W; ++p) {
-            if (p == me) continue;
-            ncclResult_t r = ncclSuccess;
-            if (n[(size_t)me]) r = ncclSend(D.rep_send, n[(size_t)me] * rb, ncclUint8, p, D.comm, D.xs);
-            if ((r == ncclSuccess || r == ncclInProgress) && n[(size_t)p])
-                r = ncclRecv(dst + off[(size_t)p] * rb, n[(size_t)p] * rb, ncclUint8, p, D.comm, D.xs);
-            if (r != ncclSuccess && r != ncclInProgress) {
-                (void)ncclGroupEnd();
-                return nccl_done(c, r, "ncclSend/ncclRecv (level all-gather)");
-            }
-        }
-        NCCLCHK(c, ncclGroupEnd());
-        return 0;
-    }
-    // host transport: this rank's block to every peer (the block repeated per destination)
-    const u64 mine = n[(size_t)me] * rb;
-    std::vector<u64> scnt((size_t)W), rcnt((size_t)W);
-    for (int p = 0; p < W; ++p) {
-        scnt[(size_t)p] = p == me ? 0 : mine;
-        rcnt[(size_t)p] = p == me ? 0 : n[(size_t)p] * rb;
-    }
-    D.stage_send.resize(std::max<u64>(mine * (u64)(W - 1), 1));
-    D.stage_recv.resize(std::max<u64>((off[(size_t)W] - n[(size_t)me]) * rb, 1));
-    if (mine) HIPCHK(c, hipMemcpyAsync(D.stage_send.data(), D.rep_send, mine, hipMemcpyDeviceToHost, D.xs));
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    if (int rc = xwait(c, D.ev_h)) return rc;
-    for (int q = 1; q < W - 1; ++q) memcpy(D.stage_send.data() + (u64)q * mine, D.stage_send.data(), mine);
-    const double th = now_s();
-    if (D.host.alltoallv(D.host.user, D.stage_send.data(), scnt.data(), D.stage_recv.data(), rcnt.data()))
-        return host_fail(c, "alltoallv (level all-gather)", th);
-    u64 o = 0;
-    for (int p = 0; p < W; ++p) {
-        if (rcnt[(size_t)p])
-            HIPCHK(c, hipMemcpyAsync(dst + off[(size_t)p] * rb, D.stage_recv.data() + o, rcnt[(size_t)p],
-                                     hipMemcpyHostToDevice, D.xs));
-        o += rcnt[(size_t)p];
-    }
-    HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-    return xwait(c, D.ev_h);
-}
+// The layout of this world's count rows, with the library's Counters in each block.
+CountRow row_layout(const rmc_ctx* c) { return CountRow{(u64)kRowWords, (u64)c->dist.world}; }
 
 float elapsed_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+}
+
+// One sharded search: what it carries from level to level, and the rounds of
+// the exchanged level in progress.
+struct Run {
+    rmc_progress_fn cb = nullptr;
+    void* user = nullptr;
+    double t0 = 0;
+    std::vector<Counters> rows;  // every rank's counters at the last level end
+    bool rows_final = false;     // the level's last count row carried every rank's final counters
+    std::vector<u64> fsz;           // every rank's frontier size (replicated levels need them all)
+    std::vector<u64> count_before;  // every rank's store count when the current level began
+    u64 total_prev = 0, generated = 0, probes = 0;
+    int depth = 0;
+    int any_cb = 0;   // some rank passed a progress callback (the per-level stop vote runs only then)
+    // Round sizing: rho = most keys one round sends one owner, per expanded
+    // state, from the previous rounds (rmc_dist_plan.h round_states, next_rho)
+    double rho = 1.0;
+    u64 vpub = 0;     // verification: states [0, vpub) are published (slot -> index)
+    bool rep_timed = false;  // a replicated level's launch awaits its timing (read after the level end)
+    // ---- the exchanged level in progress
+    u64 hi = 0, cursor = 0;             // the frontier's end; its states below cursor are expanded
+    u64 ovf_known = 0, ovf_done = 0;    // keys parked this level, as the last count row told; drained
+    u64 split_cap = 0;
+    u64 round_states[2] = {0, 0};  // states expanded by the round held in each set
+    int round_kind[2] = {0, 0};    // 0 empty, 1 expansion, 2 drain
+};
+
+// c->B with the outboxes, tickets, counts and pool of outbox set S: what the
+// kernels of a round run on (the expansion, k_route, k_drain, k_pack_counts,
+// k_materialize_remote).  Of these fields k_pack_counts reads only ocount, and
+// k_materialize_remote neither npool nor pool_cap: each gets a superset of
+// what it reads.  (A replicated level's overlay is another: B.rep, no set.)
+DevBufs set_bufs(const rmc_ctx* c, const DistState::Set& S) {
+    DevBufs B = c->B;
+    B.key_out = S.key_out;
+    B.tick_out = S.tick_out;
+    B.ocount = S.ocount;
+    B.pool = S.pool;  // tickets POOL_TICK | index name this set's pool records
+    B.npool = S.ocount + c->dist.world;
+    B.pool_cap = c->dist.pool_cap;
+    return B;
+}
+
+// Level end: the all-gathered device counters; errors stop every rank alike.
+int level_end(rmc_ctx* c, Run& R) {
+    DistState& D = c->dist;
+    D.phase = "level end (counter all-gather)";
+    if (!R.rows_final) {
+        if (int rc = allgather_counters(c, R.rows.data())) return rc;
+    }
+    R.rows_final = false;
+    *c->h_ctr = R.rows[(size_t)D.rank];
+    const LevelText text = {"verification: a fingerprint without a published state", nullptr, "", nullptr};
+    for (int r = 0; r < D.world; ++r)
+        if (int rc = level_error(c, R.rows[(size_t)r], D.lvl, text, r)) return rc;
+    return 0;
+}
+
+// The start of a search: the statistics cleared, the set begun and Init seeded
+// (rmc_recover instead restored this rank's levels, parents and set — every rank
+// of the checkpoint's world, each from its own part), the first level end, and
+// every rank's frontier size.
+int start(rmc_ctx* c, Run& R) {
+    DistState& D = c->dist;
+    const int W = D.world;
+    D.lvl = 0;
+    D.rnd = 0;
+    D.phase = "start";
+    const bool resume = c->resume != 0;
+    c->resume = 0;
+    const rmc_result saved = c->res;
+    c->res = rmc_result{};
+    c->res.set_slots = c->table_slots;
+    if (!resume) c->level_start.clear();
+    c->have_target = 0;
+    D.keys_sent = D.states_sent = D.chunks = D.parked = 0;
+    D.xfer_seconds = D.wait_seconds = 0;
+    D.rep_levels = 0;
+    if (c->B.sent) HIPCHK(c, launch_fill(c->B.sent, D.sent_slots * 8, 0, c->st));
+    // Set epochs as on one GPU.  The send-marker kernels re-derive every remote
+    // key from its materialised successor, never from a set value; SYMMETRY and
+    // verification (the lossy sent-cache kernel recovers raw keys from set
+    // values) keep an untagged set.
+    const bool verify = c->sh.verify;
+    if (!resume) {
+        if (int rc = begin_set(c, !verify && !c->sh.sym)) return rc;
+    } else {
+        HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+        c->h_ctr->count = c->level_start.back();
+    }
+    if (int rc = reset_counters(c, resume)) return rc;
+    if (!resume)  // Init is stored by its owner only
+        if (int rc = seed_init(c)) return rc;
+    R.rows.resize((size_t)W);
+    if (int rc = level_end(c, R)) return rc;
+    if (!resume) {
+        c->level_start.push_back(0);
+        c->level_start.push_back(c->h_ctr->count);
+    }
+    if (verify && !resume && c->h_ctr->count)  // slot -> store index of the initial state(s)
+        HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
+    R.count_before.resize((size_t)W);
+    for (int r = 0; r < W; ++r) {
+        R.total_prev += R.rows[(size_t)r].count;
+        R.count_before[(size_t)r] = R.rows[(size_t)r].count;
+    }
+    if (resume && R.total_prev != saved.distinct)
+        return fail(c, RMC_E_IO, "recover: the ranks' parts hold " + std::to_string(R.total_prev) +
+                                     " states, the checkpoint " + std::to_string(saved.distinct));
+    if (!resume) scan_target(c, R.rows.data(), W, 1);  // Init's violation check (level 1)
+    D.phase = "start (frontier sizes)";
+    const u64 mine[2] = {c->level_start.back() - c->level_start[c->level_start.size() - 2], R.cb ? 1ull : 0ull};
+    std::vector<u64> all(2 * (size_t)W);
+    if (int rc = allgather(c, mine, sizeof mine, all.data())) return rc;
+    R.fsz.resize((size_t)W);
+    for (int r = 0; r < W; ++r) {
+        R.fsz[(size_t)r] = all[2 * (size_t)r];
+        R.any_cb |= all[2 * (size_t)r + 1] ? 1 : 0;
+    }
+    R.generated = resume ? saved.generated : 1;
+    R.probes = resume ? saved.probes : 0;
+    R.depth = resume ? c->resume_depth : 1;
+    R.vpub = c->h_ctr->count;
+    return 0;
+}
+
+// A replicated level: every rank gathers the whole frontier (ftot states),
+// expands all of it and keeps the successors it owns; no key or state
+// exchange, one all-gather of the level's records.
+int replicated_level(rmc_ctx* c, Run& R, u64 lo, u64 hi, u64 ftot) {
+    DistState& D = c->dist;
+    const u64 RBR = (u64)(c->NW + 6) * 4;  // the level's record (RepRec)
+    D.phase = "replicated level (frontier all-gather)";
+    if (hi > lo) HIPCHK(c, launch(c, Op::PackRep, lo, hi, nullptr, D.rep_send));
+    HIPCHK(c, hipEventRecord(D.ev_c, c->st));
+    HIPCHK(c, hipStreamWaitEvent(D.xs, D.ev_c, 0));
+    if (int rc = gather_level(c, R.fsz, RBR)) return rc;
+    HIPCHK(c, hipEventRecord(D.ev_x, D.xs));
+    HIPCHK(c, hipStreamWaitEvent(c->st, D.ev_x, 0));
+    D.phase = "replicated level (expansion)";
+    DevBufs Bb = c->B;
+    Bb.rep = D.rep_buf;
+    // one launch (rep_max <= 2^24 records); timed by events read after the level end
+    HIPCHK(c, hipEventRecord(D.set[0].k0, c->st));
+    HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandRep, 0, ftot));
+    HIPCHK(c, hipEventRecord(D.set[0].k1, c->st));
+    R.rep_timed = ftot != 0;
+    c->res.expand_launches += 1;
+    D.rep_levels += 1;
+    D.chunks += 1;
+    return 0;
+}
+
+// Enqueue, on the ctx stream, the expansion (or the drain of parked keys) of
+// round k into set k & 1, once that set's last exchange has let go of it.
+int enqueue_round(rmc_ctx* c, Run& R, u64 k) {
+    DistState& D = c->dist;
+    const int W = D.world, b = (int)(k & 1);
+    const bool verify = c->sh.verify;
+    DistState::Set& S = D.set[b];
+    HIPCHK(c, hipStreamWaitEvent(c->st, S.ev_free, 0));
+    HIPCHK(c, hipMemsetAsync(S.ocount, 0, 8 * (u64)(W + 1), c->st));
+    const DevBufs Bb = set_bufs(c, S);
+    R.round_states[b] = 0;
+    R.round_kind[b] = 0;
+    S.timed = 0;
+    if (R.ovf_done < R.ovf_known) {
+        const u64 n = std::min((u64)c->B.kcap, R.ovf_known - R.ovf_done);
+        HIPCHK(c, launch_drain(Bb, R.ovf_done, n, c->st));
+        R.ovf_done += n;
+        R.round_kind[b] = 2;
+    } else if (R.cursor < R.hi) {
+        const u64 n = round_states(R.hi - R.cursor, c->B.kcap, D.fill, R.rho, R.split_cap, 1ull << kMaxLaunchLog2);
+        HIPCHK(c, hipEventRecord(S.k0, c->st));
+        HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandDist, R.cursor, R.cursor + n));
+        // the pool flush's remote successors: keyed and routed to the outboxes
+        if (W > 1 && !verify && !c->sh.sym)
+            HIPCHK(c, launch_on(c, Bb, c->st, Op::Route));
+        HIPCHK(c, hipEventRecord(S.k1, c->st));
+        S.timed = 1;
+        c->res.expand_launches += 1;
+        R.cursor += n;
+        R.round_states[b] = n;
+        R.round_kind[b] = 1;
+    }
+    if (verify) {  // publish this round's local states, then check the hits deferred to them
+        if (int rc = read_counters(c)) return rc;
+        const u64 c1 = c->h_ctr->count;
+        if (c1 > R.vpub)
+            HIPCHK(c, launch(c, Op::Publish, R.vpub, c1));
+        R.vpub = c1;
+        if (c->h_ctr->vcount) {
+            HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
+            HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
+        }
+    }
+    HIPCHK(c, hipEventRecord(S.ev_exp, c->st));
+    return 0;
+}
+
+// The count row of the round held in set S, after its expansion: packed,
+// exchanged and on its way to the pinned host row; D.ev_cnt follows it.
+int count_row(rmc_ctx* c, DistState::Set& S, bool host_more, u64 ovf_done) {
+    DistState& D = c->dist;
+    const CountRow L = row_layout(c);
+    D.phase = "count all-to-all";
+    const DevBufs Bb = set_bufs(c, S);
+    if (D.world == 1) {
+        // a world of one: the row is its own all-to-all; the pack kernel writes
+        // it (both halves) straight into the pinned host row, on the ctx stream
+        // right after the expansion: no stream hop, collective or copy
+        HIPCHK(c, hipEventRecord(S.x0, c->st));
+        HIPCHK(c, launch_pack_counts(Bb, host_more ? 1ull : 0ull, ovf_done, S.h_cx, c->st, S.h_cx + L.recv(0)));
+        HIPCHK(c, hipEventRecord(D.ev_cnt, c->st));
+        return 0;
+    }
+    HIPCHK(c, hipStreamWaitEvent(D.xs, S.ev_exp, 0));
+    HIPCHK(c, hipEventRecord(S.x0, D.xs));
+    HIPCHK(c, launch_pack_counts(Bb, host_more ? 1ull : 0ull, ovf_done, S.cx, D.xs));
+    if (int rc = a2a_u64(c, S.cx, S.cx + L.recv(0), L.words)) return rc;
+    HIPCHK(c, hipMemcpyAsync(S.h_cx, S.cx, L.len() * 8, hipMemcpyDeviceToHost, D.xs));
+    HIPCHK(c, hipEventRecord(D.ev_cnt, D.xs));
+    return 0;
+}
+
+// The level's last round, idle on this rank: when no rank sent keys in it,
+// nothing changes a counter after its count row, so the rows carry every
+// rank's final counters — no level-end all-gather.
+void take_final_rows(rmc_ctx* c, Run& R, const u64* cx, const RoundPlan& rp) {
+    if (rp.global_sends || c->sh.verify) return;
+    const CountRow L = row_layout(c);
+    for (int p = 0; p < c->dist.world; ++p) memcpy(&R.rows[(size_t)p], cx + L.recv(p) + kRowCounters, sizeof(Counters));
+    R.rows_final = true;
+}
+
+// Phase 1 of the round held in set S, on xs: keys to their owners, the owners'
+// replies back, the accepted successors into the state outboxes; then the
+// set's keys and tickets are consumed, and D.h_sa holds the phase-2 sizes.
+int phase1(rmc_ctx* c, DistState::Set& S, const RoundPlan& rp) {
+    DistState& D = c->dist;
+    const int W = D.world;
+    D.phase = "phase 1 (keys to owners)";
+    HIPCHK(c, hipMemsetAsync(D.sa, 0, 16 * (u64)W, D.xs));
+    const PeerBlocks& K = rp.keys;
+    if (int rc = a2a(c, S.key_out, K.soff, K.scnt, D.key_in, K.roff, K.rcnt)) return rc;
+    SrcOff so{};
+    for (int p = 0; p < W; ++p) so.o[p] = rp.replies.soff[p];  // the keys from p, in records
+    so.o[W] = rp.tot_in;
+    HIPCHK(c, launch_owner_insert(c->B, D.key_in, D.rep_out, rp.tot_in, so, D.sa + W, D.xs));
+    D.phase = "phase 1 (replies)";
+    const PeerBlocks& Y = rp.replies;
+    if (int rc = a2a(c, D.rep_out, Y.soff, Y.scnt, D.rep_in, Y.roff, Y.rcnt)) return rc;
+    if (rp.mx)
+        HIPCHK(c, launch_on(c, set_bufs(c, S), D.xs, Op::MaterializeRemote, rp.mx, 0,
+                            reinterpret_cast<const u32*>(D.rep_in)));
+    HIPCHK(c, hipEventRecord(S.ev_free, D.xs));  // the set's keys and tickets are consumed
+    HIPCHK(c, hipMemcpyAsync(D.h_sa, D.sa, 16 * (u64)W, hipMemcpyDeviceToHost, D.xs));
+    HIPCHK(c, hipEventRecord(D.ev_acc, D.xs));
+    return xwait(c, D.ev_acc);
+}
+
+// Phase 2, on xs: the accepted states to their owners, stored there (cx: the round's count row).
+int phase2(rmc_ctx* c, Run& R, const u64* cx) {
+    DistState& D = c->dist;
+    const u64 RB = (u64)(c->NW + 4) * 4;  // state record: packed state, global parent ref, footprint
+    const bool verify = c->sh.verify;
+    D.phase = "phase 2 (states to owners)";
+    const StatePlan sp = state_blocks(D.h_sa, cx, row_layout(c), D.rank, c->B.kcap, RB, verify);
+    if (sp.over) return fail(c, RMC_E_HIP, "phase 2: more accepted states than keys sent");
+    D.states_sent += sp.states_sent;
+    const u64 tot_st = sp.tot_st;
+    if (tot_st > (u64)D.world * c->B.kcap) return fail(c, RMC_E_CAPACITY, "phase-2 inbox full at " + where(c));
+    const PeerBlocks& T = sp.states;
+    if (int rc = a2a(c, c->B.st_out, T.soff, T.scnt, D.st_in, T.roff, T.rcnt)) return rc;
+    if (tot_st)
+        HIPCHK(c, launch_on(c, c->B, D.xs, Op::StoreRemote, tot_st, 0, D.st_in));
+    if (verify && tot_st) {  // publish the received new states, then compare the seen ones
+        HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
+        if (int rc = xwait(c, D.ev_h)) return rc;
+        if (int rc = read_counters(c)) return rc;
+        const u64 c2 = c->h_ctr->count;
+        if (c2 > R.vpub)
+            HIPCHK(c, launch_on(c, c->B, D.xs, Op::Publish, R.vpub, c2));
+        R.vpub = c2;
+        HIPCHK(c, launch_on(c, c->B, D.xs, Op::CompareRemote, tot_st, 0, D.st_in));
+        HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
+        if (int rc = xwait(c, D.ev_h)) return rc;
+    }
+    return 0;
+}
+
+// What the host does with round k's count row once it has arrived: the parked
+// keys known, the statistics, rho.  Fails alike on every rank when a rank's
+// parking buffer or this rank's inbox is full.
+int read_row(rmc_ctx* c, Run& R, u64 k, const RoundPlan& rp) {
+    DistState& D = c->dist;
+    const int b = (int)(k & 1);
+    DistState::Set& S = D.set[b];
+    if (rp.park_full >= 0)
+        return fail(c, RMC_E_CAPACITY, "exchange parking buffer full on rank " + std::to_string(rp.park_full) +
+                                           " (raise keys_per_dest) at " + where(c));
+    D.parked += rp.newly_parked;
+    R.ovf_known = std::max(R.ovf_known, rp.novf);
+    D.keys_sent += rp.keys_sent;
+    if (S.timed) {
+        c->res.expand_kernel_seconds += 1e-3 * elapsed_ms(S.k0, S.k1);
+        S.timed = 0;
+    }
+    if (D.set[b ^ 1].xtimed) {  // the previous round is complete on xs (stream order)
+        D.xfer_seconds += 1e-3 * elapsed_ms(D.set[b ^ 1].x0, D.set[b ^ 1].x1);
+        D.set[b ^ 1].xtimed = 0;
+    }
+    if (R.round_kind[b] == 1 && R.round_states[b]) R.rho = next_rho(R.rho, rp.mx, rp.newly_parked, R.round_states[b]);
+    if (D.debug)
+        fprintf(stderr, "[rmc rank %d] level %d round %llu kind %d states %llu: most keys to one owner %llu "
+                        "(cap %llu), parked %llu/%llu, in %llu, rho %.3f, more %d\n",
+                D.rank, R.depth, (unsigned long long)k, R.round_kind[b], (unsigned long long)R.round_states[b],
+                (unsigned long long)rp.mx, (unsigned long long)c->B.kcap, (unsigned long long)R.ovf_done,
+                (unsigned long long)R.ovf_known, (unsigned long long)rp.tot_in, R.rho, (int)rp.global_more);
+    if (rp.tot_in > D.in_cap) return fail(c, RMC_E_CAPACITY, "phase-1 inbox full at " + where(c));
+    return 0;
+}
+
+// An exchanged level: the frontier [lo, hi) this rank owns in rounds, until
+// no rank has more to send.  Round k lives in set k & 1; its expansion is
+// queued while round k - 1 is exchanged.
+int exchanged_level(rmc_ctx* c, Run& R, u64 lo, u64 hi) {
+    DistState& D = c->dist;
+    const int W = D.world;
+    const bool verify = c->sh.verify;
+    const CountRow L = row_layout(c);
+    R.hi = hi;
+    R.cursor = lo;
+    R.ovf_known = R.ovf_done = 0;
+    R.split_cap = split_cap(hi - lo, D.split);
+    R.round_states[0] = R.round_states[1] = 0;
+    R.round_kind[0] = R.round_kind[1] = 0;
+    if (int rc = enqueue_round(c, R, 0)) return rc;
+    for (u64 k = 0;; ++k) {
+        DistState::Set& S = D.set[k & 1];
+        D.rnd = (int)k;
+        const bool host_more = R.cursor < R.hi || R.ovf_done < R.ovf_known;
+        if (int rc = count_row(c, S, host_more, R.ovf_done)) return rc;
+        // the next round's expansion is queued before waiting, so the GPU
+        // expands while the counts travel (not in RMC_DIST_OVERLAP=0 runs)
+        bool next_queued = false;
+        if (D.overlap && host_more) {
+            if (int rc = enqueue_round(c, R, k + 1)) return rc;
+            next_queued = true;
+        }
+        if (int rc = xwait(c, D.ev_cnt)) return rc;
+        const u64* cx = S.h_cx;
+        const RoundPlan rp = decode_round(cx, L, c->B.kcap, c->B.ovf_cap, R.ovf_known, KEYB);
+        if (int rc = read_row(c, R, k, rp)) return rc;
+        if (rp.global_more && !next_queued) {
+            if (int rc = enqueue_round(c, R, k + 1)) return rc;
+        }
+        // nothing crosses this rank this round (always so at one rank): no
+        // phase 1 or 2 and no second read-back.  RCCL point-to-point groups
+        // pair ranks, so the others go on without this one; the host
+        // transport's all-to-all is a collective of every rank, so there
+        // only a world of one skips.
+        const bool idle = !verify && (D.rccl || W == 1) && rp.tot_in == 0 && rp.mx == 0;
+        hipStream_t over = D.xs;  // where the round ends
+        if (idle) {
+            over = W == 1 ? c->st : D.xs;  // where the count row ran
+            HIPCHK(c, hipEventRecord(S.ev_free, over));
+            if (!rp.global_more) take_final_rows(c, R, cx, rp);
+        } else {
+            if (int rc = phase1(c, S, rp)) return rc;
+            if (int rc = phase2(c, R, cx)) return rc;
+        }
+        HIPCHK(c, hipEventRecord(S.x1, over));
+        S.xtimed = 1;
+        D.chunks += 1;
+        if (!rp.global_more) break;
+    }
+    // expansion of the next level reads what xs stored: the ctx stream waits for it
+    HIPCHK(c, hipEventRecord(D.ev_x, D.xs));
+    HIPCHK(c, hipStreamWaitEvent(c->st, D.ev_x, 0));
+    return 0;
+}
+
+// After the level end: the timings, the totals over every rank, the next
+// level's frontier sizes, the target, and the progress vote.  *more = false when
+// the search ends here: no new states, or rank 0's callback stopped it.
+int level_totals(rmc_ctx* c, Run& R, bool* more) {
+    DistState& D = c->dist;
+    const int W = D.world;
+    *more = false;
+    if (R.rep_timed) {  // a replicated level's launch (complete: the counters were gathered after it)
+        c->res.expand_kernel_seconds += 1e-3 * elapsed_ms(D.set[0].k0, D.set[0].k1);
+        R.rep_timed = false;
+    }
+    for (auto& S : D.set)  // exchange device time of the level's last round
+        if (S.xtimed) {
+            D.xfer_seconds += 1e-3 * elapsed_ms(S.x0, S.x1);
+            S.xtimed = 0;
+        }
+    u64 tot = 0;
+    for (int r = 0; r < W; ++r) {
+        const Counters& k = R.rows[(size_t)r];
+        tot += k.count;
+        R.generated += k.generated;
+        R.probes += k.probes;
+        c->res.collisions += k.collisions;
+        c->res.verified += k.vchecked;
+        // the next level's frontier on every rank: the states it stored in this one
+        R.fsz[(size_t)r] = k.count - R.count_before[(size_t)r];
+        R.count_before[(size_t)r] = k.count;
+    }
+    const u64 nnew = tot - R.total_prev;
+    R.total_prev = tot;
+    c->level_start.push_back(c->h_ctr->count);
+    if (nnew) ++R.depth;
+    scan_target(c, R.rows.data(), W, R.depth);
+    if (R.any_cb) {  // progress: the same collective on every rank; all stop when rank 0's callback asks to
+        rmc_level_stats ls{};
+        ls.level = nnew ? R.depth - 1 : R.depth;
+        ls.generated = R.generated;
+        ls.distinct = tot;
+        ls.new_states = nnew;
+        ls.seconds = now_s() - R.t0;
+        const int stop = (R.cb && R.cb(&ls, R.user)) ? 1 : 0;
+        std::vector<int> votes((size_t)W);
+        D.phase = "progress vote";
+        if (int rc = allgather(c, &stop, sizeof stop, votes.data())) return rc;
+        if (votes[0]) {
+            c->res.left_on_queue = nnew;
+            return 0;
+        }
+    }
+    *more = nnew != 0;
+    return 0;
+}
+
+void summary(rmc_ctx* c, const Run& R) {
+    DistState& D = c->dist;
+    c->res.generated = R.generated;
+    c->res.distinct = R.total_prev;
+    c->res.depth = R.depth;
+    c->res.probes = R.probes;
+    c->res.stored_here = c->level_start.back();
+    c->res.keys_sent = D.keys_sent;
+    c->res.states_sent = D.states_sent;
+    c->res.chunks = D.chunks;
+    c->res.exchange_seconds = D.xfer_seconds;
+    c->res.exchange_wait_seconds = D.wait_seconds;
+    c->res.parked = D.parked;
+    c->res.collision_probability =
+        fp_collision_estimate((double)R.total_prev, (double)R.generated, c->table_slots, c->set_epoch != 0);
+    c->res.seconds = now_s() - R.t0;
+    D.phase = "done";
 }
 
 }  // namespace
@@ -360,16 +534,13 @@ void free_dist(rmc_ctx* c) {
         (void)hipFree(S.pool);
         (void)hipFree(S.cx);
         if (S.h_cx) (void)hipHostFree(S.h_cx);
-        for (hipEvent_t* e : {&S.ev_exp, &S.ev_free, &S.k0, &S.k1, &S.x0, &S.x1})
-            if (*e) (void)hipEventDestroy(*e);
-        S = DistState::Set{};
+        for (hipEvent_t e : {S.ev_exp, S.ev_free, S.k0, S.k1, S.x0, S.x1})
+            if (e) (void)hipEventDestroy(e);
     }
-    for (hipEvent_t* e : {&D.ev_cnt, &D.ev_acc, &D.ev_c, &D.ev_x, &D.ev_h})
-        if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+    for (hipEvent_t e : {D.ev_cnt, D.ev_acc, D.ev_c, D.ev_x, D.ev_h})
+        if (e) (void)hipEventDestroy(e);
     (void)hipFree(D.rep_send);
     (void)hipFree(D.rep_buf);
-    D.rep_send = nullptr;
-    D.rep_buf = nullptr;
     (void)hipFree(D.key_in);
     (void)hipFree(D.rep_out);
     (void)hipFree(D.rep_in);
@@ -378,520 +549,52 @@ void free_dist(rmc_ctx* c) {
     (void)hipFree(D.sa);
     if (D.h_sa) (void)hipHostFree(D.h_sa);
     (void)hipFree(D.ag_dev);
-    if (D.comm) {  // finalize (polled and bounded on a non-blocking communicator), then destroy
-        ncclResult_t r = ncclCommFinalize(D.comm);
-        const double t0 = now_s();
-        while (r == ncclInProgress && now_s() - t0 < 10.0) {
-            if (ncclCommGetAsyncError(D.comm, &r) != ncclSuccess) break;
-            if (r == ncclInProgress) std::this_thread::sleep_for(std::chrono::microseconds(50));
-        }
-        if (r == ncclSuccess) (void)ncclCommDestroy(D.comm);
-        else (void)ncclCommAbort(D.comm);
-    }
+    comm_close(c);
     if (D.xs) (void)hipStreamDestroy(D.xs);
+    // every sharded field back to its default: only the set's doubling outlives a re-shard
+    const int grown = D.table_grown;
+    D = DistState{};
+    D.table_grown = grown;
     c->B.sent = nullptr; c->B.key_out = nullptr; c->B.tick_out = nullptr; c->B.ocount = nullptr;
     c->B.st_out = nullptr; c->B.scount = nullptr; c->B.ovf = nullptr; c->B.ovf_cap = 0;
-    D.key_in = nullptr; D.rep_out = nullptr; D.rep_in = nullptr; D.st_in = nullptr; D.sa = nullptr; D.h_sa = nullptr;
-    D.ag_dev = nullptr;
-    D.ag_cap = 0;
-    D.comm = nullptr;
-    D.xs = nullptr;
-    D.on = 0;
-    D.aborted = 0;
 }
 
+// The loop of the protocol above: per level, a replicated level or rounds of
+// expansion and exchange, then the level end every rank reaches alike.
 int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     DistState& D = c->dist;
-    const int W = D.world, me = D.rank;
-    const u64 RB = (u64)(c->NW + 4) * 4;  // state record: packed state, global parent ref, footprint
-    const u64 RBR = (u64)(c->NW + 6) * 4;  // replicated-level record (RepRec)
-    const u64 kcap = c->B.kcap;
-    const double t0 = now_s();
+    Run R;
+    R.cb = cb;
+    R.user = user;
+    R.t0 = now_s();
     if (D.aborted) return fail(c, RMC_E_STATE, "sharded search: the communicator was aborted by an earlier deadline");
-    D.lvl = 0;
-    D.rnd = 0;
-    D.phase = "start";
-    // rmc_recover restored this rank's levels, parents and set (every rank of
-    // the checkpoint's world, each from its own part)
-    const bool resume = c->resume != 0;
-    c->resume = 0;
-    const rmc_result saved = c->res;
-    c->res = rmc_result{};
-    c->res.set_slots = c->table_slots;
-    if (!resume) c->level_start.clear();
-    c->have_target = 0;
-    D.keys_sent = D.states_sent = D.chunks = D.parked = 0;
-    D.xfer_seconds = D.wait_seconds = 0;
-    D.rep_levels = 0;
-    // Set epochs as on one GPU (rmc_run_bfs, raft_packed.h c_set_ep): a run after
-    // the ctx's first takes the next epoch instead of clearing the set.  The
-    // send-marker kernels re-derive every remote key from its materialised
-    // successor, never from a set value; SYMMETRY and verification (the lossy
-    // sent-cache kernel recovers raw keys from set values) keep an untagged set.
-    const char* epe = getenv("RMC_SET_EPOCH");
-    const u32 ep_max = epe ? (u32)std::min(255, std::max(0, atoi(epe))) : 255u;
-    const bool tagged = ep_max > 0 && !c->sh.verify && !c->sh.sym;
-    if (!resume) {
-        if (tagged && c->set_epoch >= 1 && c->set_epoch < ep_max) {
-            c->set_epoch += 1;
-        } else {
-            HIPCHK(c, launch_fill(c->B.table, c->table_slots * 8, 0, c->st));
-            c->set_epoch = tagged ? 1 : 0;
-        }
-    }
-    if (c->B.sent) HIPCHK(c, launch_fill(c->B.sent, D.sent_slots * 8, 0, c->st));
-    const bool verify = c->sh.verify;
-    if (verify && !resume) HIPCHK(c, launch_fill(c->B.sidx, c->table_slots * 8, 0xFF, c->st));
-    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
-    if (resume) c->h_ctr->count = c->level_start.back();
-    if (int rc = reset_counters(c, resume)) return rc;
-    // ---- Init (raft.tla:125-129): stored by its owner only
-    if (!resume) {
-        rmc_state_view iv;
-        init_view(c->cfg, &iv);
-        std::vector<u32> packed((size_t)c->NW);
-        std::string why;
-        if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
-        HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
-    }
-    std::vector<Counters> rows((size_t)W);
-    // level end: the all-gathered device counters; errors stop every rank alike
-    bool rows_final = false;  // the level's last count row carried every rank's final counters
-    auto level_end = [&]() -> int {
-        D.phase = "level end (counter all-gather)";
-        if (!rows_final) {
-            if (int rc = allgather_counters(c, rows.data())) return rc;
-        }
-        rows_final = false;
-        *c->h_ctr = rows[(size_t)me];
-        for (int r = 0; r < W; ++r) {
-            const Counters& k = rows[(size_t)r];
-            if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full on rank " + std::to_string(r));
-            if (k.overflow >> 8) return fail(c, RMC_E_CAPACITY, capacity_message(c, k.overflow, D.lvl));
-            if (k.overflow & 4u) return fail(c, RMC_E_CAPACITY, "verification buffer full on rank " + std::to_string(r));
-            if (k.overflow & 8u)
-                return fail(c, RMC_E_HIP, "verification: a fingerprint without a published state on rank " +
-                                              std::to_string(r));
-            if (k.overflow & 2u)
-                return fail(c, RMC_E_CAPACITY, "exchange parking buffer full on rank " + std::to_string(r) +
-                                                   " (raise keys_per_dest)");
-            if (k.overflow)
-                return fail(c, RMC_E_CAPACITY, "state store full on rank " + std::to_string(r) +
-                                                   " (raise rmc_config.state_capacity)");
-        }
-        return 0;
-    };
-    if (int rc = level_end()) return rc;
-    if (!resume) {
-        c->level_start.push_back(0);
-        c->level_start.push_back(c->h_ctr->count);
-    }
-    if (verify && !resume && c->h_ctr->count)  // slot -> store index of the initial state(s)
-        HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
-    u64 total_prev = 0;
-    std::vector<u64> count_before((size_t)W);  // every rank's store count when the current level began
-    for (int r = 0; r < W; ++r) {
-        total_prev += rows[(size_t)r].count;
-        count_before[(size_t)r] = rows[(size_t)r].count;
-    }
-    if (resume && total_prev != saved.distinct)
-        return fail(c, RMC_E_IO, "recover: the ranks' parts hold " + std::to_string(total_prev) +
-                                     " states, the checkpoint " + std::to_string(saved.distinct));
-    for (int r = 0; r < W && !c->have_target && !resume; ++r)  // Init's violation check (level 1)
-        if (rows[(size_t)r].viol != ~0ull) {
-            c->res.violated_inv = 1 << (int)(rows[(size_t)r].viol & 15);
-            c->res.violation_depth = 1;
-            c->have_target = 1;
-            c->target_idx = ((u64)r << 48) | (rows[(size_t)r].viol >> 4);
-        }
-    // every rank's frontier size (replicated levels need them all), and
-    // whether some rank passed a progress callback (the per-level stop vote
-    // runs only then)
-    std::vector<u64> fsz((size_t)W);
-    int any_cb = 0;
-    {
-        D.phase = "start (frontier sizes)";
-        const u64 mine[2] = {c->level_start.back() - c->level_start[c->level_start.size() - 2], cb ? 1ull : 0ull};
-        std::vector<u64> all(2 * (size_t)W);
-        if (int rc = allgather(c, mine, sizeof mine, all.data())) return rc;
-        for (int r = 0; r < W; ++r) {
-            fsz[(size_t)r] = all[2 * (size_t)r];
-            any_cb |= all[2 * (size_t)r + 1] ? 1 : 0;
-        }
-    }
-    u64 generated = resume ? saved.generated : 1, probes = resume ? saved.probes : 0;
-    int depth = resume ? c->resume_depth : 1;
+    if (int rc = start(c, R)) return rc;
     // Replicated levels: the plain kernel (every shape), models with a
     // CONSTRAINT on every field (the capacity pass reads the store)
     // (a world of one has nothing to gather: its levels run as plain rounds)
-    const bool rep_ok = W > 1 && !verify && !c->sh.sym && !c->P.unbounded && D.rep_max > 0;
-    // Round sizing: rho = most keys one round sends one owner, per expanded
-    // state, from the previous rounds (it varies along a frontier: states
-    // received from other ranks are appended after the local ones).  A round
-    // aims at an outbox half full; what does not fit is parked, not lost.
-    double rho = 1.0;
-    u64 vpub = c->h_ctr->count;  // verification: states [0, vpub) are published (slot -> index)
-    // cx: [W] sent blocks of kRowWords, [1] novf, [W] received blocks (count, flags, counters)
-    const u64 RWD = (u64)kRowWords;
-    const u64 row_len = 2 * RWD * (u64)W + 1;
-    auto rx = [&](const u64* cx, int p) { return cx + RWD * (u64)W + 1 + RWD * (u64)p; };  // block from p
-    while (!c->have_target) {
-        const u64 lo = c->level_start[(size_t)depth - 1], hi = c->level_start[(size_t)depth];
-        D.lvl = depth;
+    const bool rep_ok = D.world > 1 && !c->sh.verify && !c->sh.sym && !c->P.unbounded && D.rep_max > 0;
+    for (bool more = true; more && !c->have_target;) {
+        const u64 lo = c->level_start[(size_t)R.depth - 1], hi = c->level_start[(size_t)R.depth];
+        D.lvl = R.depth;
         D.rnd = 0;
-        if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
-            c->res.left_on_queue = 0;
-            for (u64 x : fsz) c->res.left_on_queue += x;
+        u64 ftot = 0;
+        for (u64 x : R.fsz) ftot += x;
+        if (c->cfg.max_depth > 0 && R.depth >= c->cfg.max_depth) {
+            c->res.left_on_queue = ftot;
             break;
         }
-        if (D.stall_rank == me && D.stall_level == depth) {  // test hook: this rank stops answering
-            fprintf(stderr, "[rmc rank %d] RMC_DIST_STALL_RANK: stalling %.1f s at level %d\n", me, D.stall_s, depth);
+        if (D.stall_rank == D.rank && D.stall_level == R.depth) {  // test hook: this rank stops answering
+            fprintf(stderr, "[rmc rank %d] RMC_DIST_STALL_RANK: stalling %.1f s at level %d\n", D.rank, D.stall_s,
+                    R.depth);
             std::this_thread::sleep_for(std::chrono::duration<double>(D.stall_s));
         }
         if (int rc = reset_counters(c, true)) return rc;
-        bool rep_timed = false;
-        u64 ftot = 0;
-        for (u64 x : fsz) ftot += x;
-        if (rep_ok && ftot <= D.rep_max) {
-            // ---- a replicated level: every rank gathers the whole frontier,
-            // expands all of it and keeps the successors it owns; no key or
-            // state exchange, one all-gather of the level's records
-            D.phase = "replicated level (frontier all-gather)";
-            if (hi > lo) HIPCHK(c, launch(c, Op::PackRep, lo, hi, nullptr, D.rep_send));
-            HIPCHK(c, hipEventRecord(D.ev_c, c->st));
-            HIPCHK(c, hipStreamWaitEvent(D.xs, D.ev_c, 0));
-            if (int rc = gather_level(c, fsz, RBR)) return rc;
-            HIPCHK(c, hipEventRecord(D.ev_x, D.xs));
-            HIPCHK(c, hipStreamWaitEvent(c->st, D.ev_x, 0));
-            D.phase = "replicated level (expansion)";
-            DevBufs Bb = c->B;
-            Bb.rep = D.rep_buf;
-            // one launch (rep_max <= 2^24 records); timed by events read after the level end
-            HIPCHK(c, hipEventRecord(D.set[0].k0, c->st));
-            HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandRep, 0, ftot));
-            HIPCHK(c, hipEventRecord(D.set[0].k1, c->st));
-            rep_timed = ftot != 0;
-            c->res.expand_launches += 1;
-            D.rep_levels += 1;
-            D.chunks += 1;
-        } else {
-        u64 cursor = lo, ovf_known = 0, ovf_done = 0;
-        const u64 frontier = hi - lo;
-        // at least D.split rounds for a large level, so one round's count
-        // exchange and read-back overlap the next round's expansion
-        const u64 split_cap = frontier >= (1ull << 21) ? (frontier + D.split - 1) / (u64)D.split : frontier;
-        u64 round_states[2] = {0, 0};  // states expanded by the round held in each set
-        int round_kind[2] = {0, 0};    // 0 empty, 1 expansion, 2 drain
-        // enqueue the expansion (or the drain of parked keys) of round k into set k & 1
-        auto enqueue_A = [&](u64 k) -> int {
-            DistState::Set& S = D.set[k & 1];
-            HIPCHK(c, hipStreamWaitEvent(c->st, S.ev_free, 0));
-            HIPCHK(c, hipMemsetAsync(S.ocount, 0, 8 * (u64)(W + 1), c->st));
-            DevBufs Bb = c->B;
-            Bb.key_out = S.key_out;
-            Bb.tick_out = S.tick_out;
-            Bb.ocount = S.ocount;
-            Bb.pool = S.pool;
-            Bb.npool = S.ocount + W;
-            Bb.pool_cap = D.pool_cap;
-            round_states[k & 1] = 0;
-            round_kind[k & 1] = 0;
-            S.timed = 0;
-            if (ovf_done < ovf_known) {
-                const u64 n = std::min(kcap, ovf_known - ovf_done);
-                HIPCHK(c, launch_drain(Bb, ovf_done, n, c->st));
-                ovf_done += n;
-                round_kind[k & 1] = 2;
-            } else if (cursor < hi) {
-                const u64 target = (u64)(D.fill * (double)kcap / std::max(rho, 0.02));
-                // the rest of the level in equal rounds of at most this size (not full
-                // rounds and a small remainder: a small round idles most of the grid)
-                const u64 cap = std::max<u64>(1, std::min<u64>({1ull << kMaxLaunchLog2, target, split_cap}));
-                const u64 rest = hi - cursor, nr = (rest + cap - 1) / cap;
-                const u64 n = (rest + nr - 1) / nr;
-                HIPCHK(c, hipEventRecord(S.k0, c->st));
-                HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandDist, cursor, cursor + n));
-                // the pool flush's remote successors: keyed and routed to the outboxes
-                if (W > 1 && !verify && !c->sh.sym)
-                    HIPCHK(c, launch_on(c, Bb, c->st, Op::Route));
-                HIPCHK(c, hipEventRecord(S.k1, c->st));
-                S.timed = 1;
-                c->res.expand_launches += 1;
-                cursor += n;
-                round_states[k & 1] = n;
-                round_kind[k & 1] = 1;
-            }
-            if (verify) {  // publish this round's local states, then check the hits deferred to them
-                if (int rc = read_counters(c)) return rc;
-                const u64 c1 = c->h_ctr->count;
-                if (c1 > vpub)
-                    HIPCHK(c, launch(c, Op::Publish, vpub, c1));
-                vpub = c1;
-                if (c->h_ctr->vcount) {
-                    HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
-                    HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
-                }
-            }
-            HIPCHK(c, hipEventRecord(S.ev_exp, c->st));
-            return 0;
-        };
-        std::vector<u64> soff((size_t)W), scnt((size_t)W), roff((size_t)W), rcnt((size_t)W);
-        std::vector<u64> s2((size_t)W), o2((size_t)W), r2((size_t)W), q2((size_t)W);
-        if (int rc = enqueue_A(0)) return rc;
-        for (u64 k = 0;; ++k) {
-            const int b = (int)(k & 1);
-            DistState::Set& S = D.set[b];
-            D.rnd = (int)k;
-            const bool host_more = cursor < hi || ovf_done < ovf_known;
-            // ---- count row of round k (after its expansion), on xs
-            D.phase = "count all-to-all";
-            if (W == 1) {
-                // a world of one: the row is its own all-to-all; the pack kernel writes
-                // it (both halves) straight into the pinned host row, on the ctx stream
-                // right after the expansion: no stream hop, collective or copy
-                HIPCHK(c, hipEventRecord(S.x0, c->st));
-                DevBufs Bb = c->B;
-                Bb.ocount = S.ocount;
-                HIPCHK(c, launch_pack_counts(Bb, host_more ? 1ull : 0ull, ovf_done, S.h_cx, c->st,
-                                             S.h_cx + RWD * (u64)W + 1));
-                HIPCHK(c, hipEventRecord(D.ev_cnt, c->st));
-            } else {
-                HIPCHK(c, hipStreamWaitEvent(D.xs, S.ev_exp, 0));
-                HIPCHK(c, hipEventRecord(S.x0, D.xs));
-                {
-                    DevBufs Bb = c->B;
-                    Bb.ocount = S.ocount;
-                    HIPCHK(c, launch_pack_counts(Bb, host_more ? 1ull : 0ull, ovf_done, S.cx, D.xs));
-                }
-                if (int rc = a2a_u64(c, S.cx, S.cx + RWD * (u64)W + 1, RWD)) return rc;
-                HIPCHK(c, hipMemcpyAsync(S.h_cx, S.cx, row_len * 8, hipMemcpyDeviceToHost, D.xs));
-                HIPCHK(c, hipEventRecord(D.ev_cnt, D.xs));
-            }
-            // the next round's expansion is queued before waiting, so the GPU
-            // expands while the counts travel (not in RMC_DIST_OVERLAP=0 runs)
-            bool next_queued = false;
-            if (D.overlap && host_more) {
-                if (int rc = enqueue_A(k + 1)) return rc;
-                next_queued = true;
-            }
-            if (int rc = xwait(c, D.ev_cnt)) return rc;
-            const u64* cx = S.h_cx;
-            // a rank whose parking buffer overflowed says so in its flags (bit 1):
-            // every rank sees every row and stops here alike
-            for (int p = 0; p < W; ++p)
-                if (rx(cx, p)[1] & 2u)
-                    return fail(c, RMC_E_CAPACITY, "exchange parking buffer full on rank " + std::to_string(p) +
-                                                       " (raise keys_per_dest) at " + where(c));
-            const u64 novf = std::min(cx[RWD * (u64)W], c->B.ovf_cap);  // never drain past the buffer
-            const u64 newly_parked = novf - std::min(novf, ovf_known);
-            D.parked += newly_parked;
-            ovf_known = std::max(ovf_known, novf);
-            bool global_more = false, global_sends = false;
-            u64 mx = 0, tot_in = 0;
-            for (int p = 0; p < W; ++p) {
-                global_more |= (rx(cx, p)[1] & 1u) != 0;
-                global_sends |= (rx(cx, p)[1] & 4u) != 0;
-                // phase-1 key records: the raw fingerprint (k, s32), KEYB bytes each
-                scnt[(size_t)p] = cx[RWD * (u64)p] * KEYB;
-                soff[(size_t)p] = (u64)p * kcap * KEYB;
-                rcnt[(size_t)p] = rx(cx, p)[0] * KEYB;
-                roff[(size_t)p] = tot_in * KEYB;
-                tot_in += rx(cx, p)[0];
-                mx = std::max(mx, cx[RWD * (u64)p]);
-                D.keys_sent += cx[RWD * (u64)p];
-            }
-            if (S.timed) {
-                c->res.expand_kernel_seconds += 1e-3 * elapsed_ms(S.k0, S.k1);
-                S.timed = 0;
-            }
-            if (D.set[b ^ 1].xtimed) {  // the previous round is complete on xs (stream order)
-                D.xfer_seconds += 1e-3 * elapsed_ms(D.set[b ^ 1].x0, D.set[b ^ 1].x1);
-                D.set[b ^ 1].xtimed = 0;
-            }
-            if (round_kind[b] == 1 && round_states[b])  // keys per state of the fullest owner (parked ones included)
-                rho = std::max(0.5 * rho, (double)(mx + newly_parked) / (double)round_states[b]);
-            if (D.debug)
-                fprintf(stderr, "[rmc rank %d] level %d round %llu kind %d states %llu: most keys to one owner %llu "
-                                "(cap %llu), parked %llu/%llu, in %llu, rho %.3f, more %d\n",
-                        me, depth, (unsigned long long)k, round_kind[b], (unsigned long long)round_states[b],
-                        (unsigned long long)mx, (unsigned long long)kcap, (unsigned long long)ovf_done,
-                        (unsigned long long)ovf_known, (unsigned long long)tot_in, rho, (int)global_more);
-            if (tot_in > D.in_cap) return fail(c, RMC_E_CAPACITY, "phase-1 inbox full at " + where(c));
-            if (global_more && !next_queued) {
-                if (int rc = enqueue_A(k + 1)) return rc;
-                next_queued = true;
-            }
-            // nothing crosses this rank this round (always so at one rank): no
-            // phase 1 or 2 and no second read-back.  RCCL point-to-point groups
-            // pair ranks, so the others go on without this one; the host
-            // transport's all-to-all is a collective of every rank, so there
-            // only a world of one skips.
-            bool idle = !verify && (D.rccl || W == 1) && tot_in == 0;
-            for (int p = 0; p < W; ++p) idle = idle && scnt[(size_t)p] == 0;
-            if (idle) {
-                hipStream_t is = W == 1 ? c->st : D.xs;  // where the count row ran
-                HIPCHK(c, hipEventRecord(S.ev_free, is));
-                HIPCHK(c, hipEventRecord(S.x1, is));
-                S.xtimed = 1;
-                D.chunks += 1;
-                if (!global_more) {
-                    // the level's last round and no rank sent keys in it: nothing
-                    // changes a counter after its count row, so the rows carry
-                    // every rank's final counters — no level-end all-gather
-                    if (!global_sends && !verify) {
-                        for (int p = 0; p < W; ++p) memcpy(&rows[(size_t)p], rx(cx, p) + 2, sizeof(Counters));
-                        rows_final = true;
-                    }
-                    break;
-                }
-                continue;
-            }
-            // ---- phase 1: keys to their owners, replies back; phase 2 sizes
-            D.phase = "phase 1 (keys to owners)";
-            HIPCHK(c, hipMemsetAsync(D.sa, 0, 16 * (u64)W, D.xs));
-            if (int rc = a2a(c, S.key_out, soff.data(), scnt.data(), D.key_in, roff.data(), rcnt.data())) return rc;
-            SrcOff so{};
-            for (int p = 0; p < W; ++p) so.o[p] = roff[(size_t)p] / KEYB;
-            so.o[W] = tot_in;
-            HIPCHK(c, launch_owner_insert(c->B, D.key_in, D.rep_out, tot_in, so, D.sa + W, D.xs));
-            for (int p = 0; p < W; ++p) {  // block p of rep_out (keys from p) back to p; from d into rep_in + d * kcap
-                s2[(size_t)p] = rcnt[(size_t)p] / KEYB;
-                o2[(size_t)p] = roff[(size_t)p] / KEYB;
-                r2[(size_t)p] = scnt[(size_t)p] / KEYB;
-                q2[(size_t)p] = (u64)p * kcap;
-            }
-            D.phase = "phase 1 (replies)";
-            if (int rc = a2a(c, D.rep_out, o2.data(), s2.data(), D.rep_in, q2.data(), r2.data())) return rc;
-            if (mx) {
-                DevBufs Bb = c->B;
-                Bb.key_out = S.key_out;
-                Bb.tick_out = S.tick_out;
-                Bb.ocount = S.ocount;
-                Bb.pool = S.pool;  // tickets POOL_TICK | index name this set's pool records
-                HIPCHK(c, launch_on(c, Bb, D.xs, Op::MaterializeRemote, mx, 0, reinterpret_cast<const u32*>(D.rep_in)));
-            }
-            HIPCHK(c, hipEventRecord(S.ev_free, D.xs));  // the set's keys and tickets are consumed
-            HIPCHK(c, hipMemcpyAsync(D.h_sa, D.sa, 16 * (u64)W, hipMemcpyDeviceToHost, D.xs));
-            HIPCHK(c, hipEventRecord(D.ev_acc, D.xs));
-            if (int rc = xwait(c, D.ev_acc)) return rc;
-            // ---- phase 2: the accepted states
-            D.phase = "phase 2 (states to owners)";
-            u64 tot_st = 0;
-            for (int p = 0; p < W; ++p) {
-                // verification ships every key's state (the seen ones to be compared)
-                const u64 ns = D.h_sa[p], nr = verify ? rx(cx, p)[0] : D.h_sa[W + p];
-                if (p != me && ns > kcap) return fail(c, RMC_E_HIP, "phase 2: more accepted states than keys sent");
-                soff[(size_t)p] = (u64)p * kcap * RB;
-                scnt[(size_t)p] = p == me ? 0 : ns * RB;
-                rcnt[(size_t)p] = p == me ? 0 : nr * RB;
-                roff[(size_t)p] = tot_st * RB;
-                tot_st += rcnt[(size_t)p] / RB;
-                if (p != me) D.states_sent += ns;
-            }
-            if (tot_st > (u64)W * kcap) return fail(c, RMC_E_CAPACITY, "phase-2 inbox full at " + where(c));
-            if (int rc = a2a(c, c->B.st_out, soff.data(), scnt.data(), D.st_in, roff.data(), rcnt.data())) return rc;
-            if (tot_st)
-                HIPCHK(c, launch_on(c, c->B, D.xs, Op::StoreRemote, tot_st, 0, D.st_in));
-            if (verify && tot_st) {  // publish the received new states, then compare the seen ones
-                HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-                if (int rc = xwait(c, D.ev_h)) return rc;
-                if (int rc = read_counters(c)) return rc;
-                const u64 c2 = c->h_ctr->count;
-                if (c2 > vpub)
-                    HIPCHK(c, launch_on(c, c->B, D.xs, Op::Publish, vpub, c2));
-                vpub = c2;
-                HIPCHK(c, launch_on(c, c->B, D.xs, Op::CompareRemote, tot_st, 0, D.st_in));
-                HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
-                if (int rc = xwait(c, D.ev_h)) return rc;
-            }
-            HIPCHK(c, hipEventRecord(S.x1, D.xs));
-            S.xtimed = 1;
-            D.chunks += 1;
-            if (!global_more) break;
-        }
-        // expansion of the next level reads what xs stored: the ctx stream waits for it
-        HIPCHK(c, hipEventRecord(D.ev_x, D.xs));
-        HIPCHK(c, hipStreamWaitEvent(c->st, D.ev_x, 0));
-        }
-        if (int rc = level_end()) return rc;
-        if (rep_timed) {  // a replicated level's launch (complete: the counters were gathered after it)
-            c->res.expand_kernel_seconds += 1e-3 * elapsed_ms(D.set[0].k0, D.set[0].k1);
-            rep_timed = false;
-        }
-        for (auto& S2 : D.set)  // exchange device time of the level's last round
-            if (S2.xtimed) {
-                D.xfer_seconds += 1e-3 * elapsed_ms(S2.x0, S2.x1);
-                S2.xtimed = 0;
-            }
-        u64 tot = 0, gen = 0, pr = 0;
-        for (int r = 0; r < W; ++r) {
-            const Counters& k = rows[(size_t)r];
-            tot += k.count;
-            gen += k.generated;
-            pr += k.probes;
-            c->res.collisions += k.collisions;
-            c->res.verified += k.vchecked;
-        }
-        const u64 nnew = tot - total_prev;
-        total_prev = tot;
-        generated += gen;
-        probes += pr;
-        // the next level's frontier on every rank: the states it stored in this one
-        for (int r = 0; r < W; ++r) {
-            fsz[(size_t)r] = rows[(size_t)r].count - count_before[(size_t)r];
-            count_before[(size_t)r] = rows[(size_t)r].count;
-        }
-        c->level_start.push_back(c->h_ctr->count);
-        if (nnew) ++depth;
-        for (int r = 0; r < W && !c->have_target; ++r)  // the lowest rank's least violating index
-            if (rows[(size_t)r].viol != ~0ull) {
-                c->res.violated_inv = 1 << (int)(rows[(size_t)r].viol & 15);
-                c->res.violation_depth = depth;
-                c->have_target = 1;
-                c->target_idx = ((u64)r << 48) | (rows[(size_t)r].viol >> 4);
-            }
-        if (!c->have_target && (c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK))
-            for (int r = 0; r < W && !c->have_target; ++r)
-                if (rows[(size_t)r].deadlock != ~0ull) {
-                    c->res.deadlock = 1;
-                    c->have_target = 1;
-                    c->target_idx = ((u64)r << 48) | rows[(size_t)r].deadlock;
-                }
-        if (any_cb) {  // progress: the same collective on every rank; all stop when rank 0's callback asks to
-            rmc_level_stats ls{};
-            ls.level = nnew ? depth - 1 : depth;
-            ls.generated = generated;
-            ls.distinct = tot;
-            ls.new_states = nnew;
-            ls.seconds = now_s() - t0;
-            const int stop = (cb && cb(&ls, user)) ? 1 : 0;
-            std::vector<int> votes((size_t)W);
-            D.phase = "progress vote";
-            if (int rc = allgather(c, &stop, sizeof stop, votes.data())) return rc;
-            if (votes[0]) {
-                c->res.left_on_queue = nnew;
-                break;
-            }
-        }
-        if (!nnew) break;
+        if (int rc = rep_ok && ftot <= D.rep_max ? replicated_level(c, R, lo, hi, ftot) : exchanged_level(c, R, lo, hi))
+            return rc;
+        if (int rc = level_end(c, R)) return rc;
+        if (int rc = level_totals(c, R, &more)) return rc;
     }
-    // ---- global summary
-    c->res.generated = generated;
-    c->res.distinct = total_prev;
-    c->res.depth = depth;
-    c->res.probes = probes;
-    c->res.stored_here = c->level_start.back();
-    c->res.keys_sent = D.keys_sent;
-    c->res.states_sent = D.states_sent;
-    c->res.chunks = D.chunks;
-    c->res.exchange_seconds = D.xfer_seconds;
-    c->res.exchange_wait_seconds = D.wait_seconds;
-    c->res.parked = D.parked;
-    const double Dd = (double)total_prev, G = (double)generated;
-    c->res.collision_probability = fp_collision_estimate(Dd, G, c->table_slots, c->set_epoch != 0);
-    c->res.seconds = now_s() - t0;
-    D.phase = "done";
+    summary(c, R);
     return 0;
 }
 
@@ -947,15 +650,6 @@ int trace_sharded(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t
 
 extern "C" {
 
-int rmc_rccl_unique_id(uint8_t id[128]) {
-    if (!id) return RMC_E_INVAL;
-    ncclUniqueId u;
-    if (ncclGetUniqueId(&u) != ncclSuccess) return RMC_E_HIP;
-    static_assert(sizeof u == 128, "ncclUniqueId is 128 bytes");
-    memcpy(id, &u, 128);
-    return 0;
-}
-
 int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, const rmc_transport* host,
               uint64_t keys_per_dest, uint64_t sent_cache_slots) {
     if (!c || world < 1 || world > kMaxWorld || rank < 0 || rank >= world) return RMC_E_INVAL;
@@ -995,9 +689,9 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
     D.pool_cap = world > 1 ? W * kcap : 64;
     for (auto& S : D.set) {
         ok = ok && hipMalloc(&S.key_out, W * kcap * KEYB) == hipSuccess && hipMalloc(&S.tick_out, W * kcap * 8) == hipSuccess &&
-             hipMalloc(&S.ocount, 8 * (W + 1)) == hipSuccess && hipMalloc(&S.cx, 8 * (2 * kRowWords * W + 1)) == hipSuccess &&
+             hipMalloc(&S.ocount, 8 * (W + 1)) == hipSuccess && hipMalloc(&S.cx, 8 * row_layout(c).len()) == hipSuccess &&
              hipMalloc(&S.pool, D.pool_cap * RB) == hipSuccess &&
-             hipHostMalloc(&S.h_cx, 8 * (2 * kRowWords * W + 1), hipHostMallocDefault) == hipSuccess;
+             hipHostMalloc(&S.h_cx, 8 * row_layout(c).len(), hipHostMallocDefault) == hipSuccess;
         for (hipEvent_t* e : {&S.ev_exp, &S.ev_free})
             ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
         for (hipEvent_t* e : {&S.k0, &S.k1, &S.x0, &S.x1}) ok = ok && hipEventCreate(e) == hipSuccess;
@@ -1078,91 +772,13 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
     D.lvl = 0;
     D.rnd = 0;
     D.phase = "communicator init";
-    if (D.rccl) {
-        ncclUniqueId u;
-        memcpy(&u, rccl_id, sizeof u);
-        // non-blocking (RMC_DIST_NCCL_BLOCKING=1: the blocking mode, A/B): every
-        // call is polled under the deadline, connection set-up included
-        D.nonblocking = 1;
-        if (const char* e = getenv("RMC_DIST_NCCL_BLOCKING")) D.nonblocking = atoi(e) ? 0 : 1;
-        ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
-        cfg.blocking = D.nonblocking ? 0 : 1;
-        // The whole set-up — the init call and, on the non-blocking communicator,
-        // its completion — runs on a helper thread (on this ctx's device) that
-        // lives until it is complete (RCCL's group state of a call is the calling
-        // thread's), waited for here under the deadline: the call does not
-        // promise to return at once for every bootstrap state (a peer that never
-        // connects).  On expiry the helper, which owns the communicator, aborts it
-        // itself once it leaves its poll loop (no other thread frees it while the
-        // helper may still be polling it); this thread waits for that, bounded
-        // (kAbortWait), and a call that never returns is left to the process exit.
-        struct Init {
-            std::atomic<int> done{0}, quit{0}, aborted{0};
-            std::atomic<ncclComm_t> comm{nullptr};
-            ncclResult_t r = ncclSuccess;
-        };
-        auto in = std::make_shared<Init>();
-        const int dev = c->cfg.device;
-        const bool nb = D.nonblocking != 0;
-        std::thread([in, world, u, rank, cfg, dev, nb]() mutable {
-            (void)hipSetDevice(dev);
-            ncclComm_t cm = nullptr;
-            ncclResult_t r = ncclCommInitRankConfig(&cm, world, u, rank, &cfg);
-            in->comm.store(cm);
-            while (nb && r == ncclInProgress && cm && !in->quit.load()) {
-                ncclResult_t a = ncclSuccess;
-                if (ncclCommGetAsyncError(cm, &a) != ncclSuccess) break;
-                r = a;
-                if (r == ncclInProgress) std::this_thread::sleep_for(std::chrono::microseconds(50));
-            }
-            if (in->quit.load() && cm) {  // the waiting thread gave up: the owner aborts
-                (void)ncclCommAbort(cm);
-                in->aborted.store(1);
-            }
-            in->r = r;
-            in->done.store(1);
-        }).detach();
-        const double t_init = now_s();
-        while (!in->done.load()) {
-            if (now_s() - t_init > D.timeout_s) {
-                in->quit.store(1);
-                const double t_q = now_s();
-                while (!in->done.load() && now_s() - t_q < kAbortWait)
-                    std::this_thread::sleep_for(std::chrono::milliseconds(1));
-                const bool returned = in->comm.load() != nullptr;
-                bool aborted = in->aborted.load() != 0;
-                if (in->done.load() && !aborted && returned) {
-                    // the helper completed the init just before it saw quit: it has
-                    // left the communicator, so it is aborted here
-                    aborted = abort_bounded(in->comm.load());
-                }
-                D.comm = nullptr;  // never touched again by this thread
-                const int rc = deadline_fail(c,
-                                             returned ? "ncclCommInitRankConfig (waiting for every rank)"
-                                                      : "ncclCommInitRankConfig (the call has not returned)",
-                                             !returned || aborted ? 0 : 1);
-                const std::string msg = c->err;
-                free_dist(c);
-                c->err = msg;
-                return rc;
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-        D.comm = in->comm.load();
-        ncclResult_t r = in->r;
-        if (r != ncclSuccess && r != ncclInProgress) {
-            if (D.comm) (void)abort_bounded(D.comm);
-            D.comm = nullptr;
-            free_dist(c);
-            return fail(c, RMC_E_HIP, std::string("ncclCommInitRankConfig: ") + ncclGetErrorString(r));
-        }
-        if (int rc = nccl_done(c, r, "ncclCommInitRankConfig (waiting for every rank)")) {
+    if (D.rccl)
+        if (int rc = comm_init(c, rccl_id)) {
             const std::string msg = c->err;
             free_dist(c);
             c->err = msg;
             return rc;
         }
-    }
     D.on = 1;
     return 0;
 }

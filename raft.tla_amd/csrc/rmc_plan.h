@@ -1,6 +1,7 @@
 // rmc_plan.h — how a packed ctx divides its HBM budget (rmc_create, rmc_api.cpp):
 // states, fingerprint-set slots, spill window, where the trace links live; and
-// the launch sizing of the ring window, shared with the wide layout.  Host
+// the launch sizing of the ring window, shared with the wide layout; and the set
+// epoch a run takes (single-GPU and sharded, tests/native/dist_plan_check.cpp).  Host
 // arithmetic only (no HIP, no getenv), so a host test can check it
 // (tests/native/packed_plan_check.cpp against tests/golden/packed_plan_cases.txt).
 #pragma once
@@ -17,6 +18,22 @@ inline uint64_t set_slots_of(uint64_t bytes) {
     uint64_t sl = 1024;
     while ((sl << 1) * 8 <= bytes) sl <<= 1;
     return sl;
+}
+
+// The set epoch of a run (raft_packed.h c_set_ep).  A run on a ctx whose set holds
+// the tagged entries of an earlier run takes the next epoch and clears nothing:
+// their slots read as empty.  The first run of a ctx, every ep_max-th one and a
+// run that cannot tag its set (tagged = false: verification, whose slot -> state
+// map is cleared anyway; sharded SYMMETRY, whose sent-cache kernel recovers raw
+// keys from set values) clear the set.  ep_max is RMC_SET_EPOCH (255; 0: every
+// run clears).  Epoch 0 is an untagged set.
+struct SetEpoch {
+    uint32_t epoch;  // the epoch to run with
+    bool clear;      // clear the set first
+};
+inline SetEpoch next_set_epoch(uint32_t current, uint32_t ep_max, bool tagged) {
+    if (ep_max > 0 && tagged && current >= 1 && current < ep_max) return {current + 1, false};
+    return {ep_max > 0 && tagged ? 1u : 0u, true};
 }
 
 struct PackedPlanIn {

@@ -18,7 +18,7 @@ Per extrapolated level: t1 = f + frontier * tau (tau: seconds per frontier
 state over the prefix's last 3 levels), keys to owners = frontier * kappa
 (kappa: keys sent per expanded state over the prefix's last 3 levels, from
 the rehearsal), rounds = ceil(frontier / N / min(2^25, kcap / rho)) with rho =
-kappa / N keys per state to one owner (librmc's round sizing, rmc_dist.cpp).
+kappa / N keys per state to one owner (librmc's round sizing, rmc_dist_plan.h).
 
     python tools/bench8_plan.py prefix_levels.jsonl prefix_rounds.txt prefix_dist8.json shape_levels.jsonl [N]
         [--sizing profiles/r03/sizing_next_bounds.txt] [--k-dist K] [--measured full_levels.jsonl]

@@ -24,8 +24,9 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 8 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
-                             rmc_result.set_slots (round 6) */
+#define RMC_ABI_VERSION 9 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+                             rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
+                             rmc_coverage_action (round 8) */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -110,6 +111,11 @@ extern "C" {
 #define RMC_FLAG_UNBOUNDED_DUP (1u << 8)   /* no CONSTRAINT on messages[m]               */
 #define RMC_UNBOUNDED_ANY (RMC_FLAG_UNBOUNDED_TERM | RMC_FLAG_UNBOUNDED_LOG | RMC_FLAG_UNBOUNDED_MSGS | \
                            RMC_FLAG_UNBOUNDED_DUP)
+#define RMC_FLAG_COVERAGE (1u << 9)        /* action coverage (TLC -coverage): per-action  */
+                                           /* generated / distinct counts of the BFS, read */
+                                           /* with rmc_get_coverage.  Single GPU, both     */
+                                           /* layouts; no checkpoint / recover; ignored by */
+                                           /* rmc_simulate                                 */
 
 /* rmc_config.invariants — the INVARIANT names the engine knows (fused checks). */
 #define RMC_INV_TYPEOK (1u << 0)           /* raft.tla:482-492                          */
@@ -283,6 +289,43 @@ int rmc_get_result(const rmc_ctx* ctx, rmc_result* out);
  * bits (1..64), so collisions happen and must be reported.  Needs
  * RMC_FLAG_VERIFY_STATES. */
 int rmc_set_fp_bits(rmc_ctx* ctx, int32_t bits);
+
+/* ---- action coverage (TLC -coverage) ---------------------------------------
+ * With RMC_FLAG_COVERAGE the BFS tallies, for every action of Next, how many
+ * successors it generated and how many of the stored states it produced: TLC's
+ * per-action "distinct:generated" statistics.  The rows, in this fixed order:
+ * Init; the seven server families Restart, Timeout, RequestVote, BecomeLeader,
+ * ClientRequest, AdvanceCommitIndex, AppendEntries; the five disjuncts of
+ * Receive (raft.tla:393-403), which TLC treats as separate actions: UpdateTerm
+ * (the message's term is newer than its receiver's) and Receive:<mtype> for
+ * the four message types; DuplicateMessage; DropMessage.
+ *  - generated[a]: every enabled lane of action a over every expanded state,
+ *    the notion of rmc_result.generated (stuttering and out-of-CONSTRAINT
+ *    successors count).  Deterministic.
+ *  - distinct[a]: the stored states whose producing lane is of action a.  A
+ *    state reached by two actions in the same launch is credited to the lane
+ *    that won the set insert (TLC with several workers does the same), so a
+ *    distinct[a] may differ between runs, between the number of new states
+ *    only a reaches and the number a reaches at all.
+ *  - row Init: the initial states generated and stored.
+ * Whenever rmc_run_bfs returns 0 (fixpoint, max_depth, a callback stop, a
+ * violation, a deadlock) the generated[] sum to rmc_result.generated and the
+ * distinct[] to rmc_result.distinct.  Every rmc_run_bfs starts from zero
+ * tallies.  The counting is a pass of its own after each expansion launch (the
+ * expansion kernels are unchanged); without the flag nothing is allocated,
+ * launched or read back for it.
+ * rmc_get_coverage: RMC_E_STATE on a ctx without the flag or before a run.
+ * rmc_coverage_action: the name of a row, for rows 1..14 the key
+ * rmc_action_location accepts ("Init" for row 0); NULL out of range.
+ * rmc_shard on a ctx with the flag is RMC_E_INVAL, rmc_checkpoint and
+ * rmc_recover RMC_E_STATE (the tallies are of whole runs and are not written). */
+#define RMC_COV_ACTIONS 15
+typedef struct rmc_coverage {
+    uint64_t generated[RMC_COV_ACTIONS];
+    uint64_t distinct[RMC_COV_ACTIONS];
+} rmc_coverage;
+int rmc_get_coverage(const rmc_ctx* ctx, rmc_coverage* out);
+const char* rmc_coverage_action(int32_t row);
 
 /* Counterexample: the states from an initial state to the violating (or
  * deadlocked) state, in order, with the action family and lane of the step
@@ -477,8 +520,8 @@ int rmc_sim_config_from_files(const char* cfg_path, const char* tla_path, rmc_co
  * headers print it (`State k: <Action line L1, col C1 to line L2, col C2 of
  * module raft>`): the body of the action's definition.  `action` is a family
  * name of rmc.h's lane table, "UpdateTerm", or "Receive:<mtype>" for the
- * Receive disjunct of that message type (raft.tla:393-403).  out4 = L1, C1,
- * L2, C2. */
+ * Receive disjunct of that message type (raft.tla:393-403); "Init" gives the
+ * initial predicate's body (raft.tla:125-129).  out4 = L1, C1, L2, C2. */
 int rmc_action_location(const char* action, int32_t* out4);
 
 #ifdef __cplusplus

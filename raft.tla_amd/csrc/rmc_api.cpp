@@ -13,6 +13,7 @@
 
 #include <sys/mman.h>
 
+#include "rmc_cover.h"
 #include "rmc_ctx.h"
 
 using namespace rmc;
@@ -33,7 +34,7 @@ int validate(const rmc_config* c, std::string* why) {
     if (c->n_servers < 2 || c->n_servers > RMC_MAX_SERVERS) return bad("n_servers must be 2..5");
     if (c->n_values < 1 || c->n_values > RMC_MAX_VALUES) return bad("n_values must be 1..2");
     if (c->invariants & ~1023u) return bad("unknown invariant bit");
-    if (c->flags & ~511u) return bad("unknown flag bit");
+    if (c->flags & ~1023u) return bad("unknown flag bit");
     if ((c->flags & RMC_UNBOUNDED_ANY) && c->max_depth <= 0)
         return bad("a model with unbounded fields (RMC_FLAG_UNBOUNDED_*) needs max_depth > 0 (TLC -depth)");
     if (wide_wanted(*c)) return validate_wide(c, why);  // bounds beyond the packed capacity
@@ -137,6 +138,21 @@ int seed_init(rmc_ctx* c) {
     if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
+    return 0;
+}
+
+static_assert(COV_ROWS == RMC_COV_ACTIONS, "rmc_cover.h's rows are rmc.h's");
+
+int cover_begin(rmc_ctx* c) {
+    c->cov_valid = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_cov, 0, sizeof(rmc_coverage), c->st));
+    return 0;
+}
+
+int cover_end(rmc_ctx* c) {
+    HIPCHK(c, hipMemcpyAsync(&c->cov, c->d_cov, sizeof(rmc_coverage), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    c->cov_valid = 1;
     return 0;
 }
 
@@ -274,6 +290,10 @@ int rmc_create(const rmc_config* cfg, rmc_ctx** out) {
         return bail(RMC_E_NOMEM);
     }
     memset(c->h_ctr, 0, sizeof(Counters));
+    if (cover_on(c) && hipMalloc(&c->d_cov, sizeof(rmc_coverage)) != hipSuccess) {
+        c->err = "device allocation failed (coverage tallies)";
+        return bail(RMC_E_NOMEM);
+    }
     if (c->wide) {  // bounds beyond the packed capacity: the wide layout (rmc_wide.cpp)
         if (int rc = create_wide(c)) return bail(rc);
         *out = c;
@@ -385,6 +405,7 @@ void rmc_destroy(rmc_ctx* c) {
     if (c->spill.h_ostage) (void)hipHostFree(c->spill.h_ostage);
     if (c->spill.hs_bytes) munmap(c->spill.h_state, c->spill.hs_bytes);
     (void)hipFree(c->B.ties);
+    (void)hipFree(c->d_cov);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -408,6 +429,8 @@ static int start_run(rmc_ctx* c, int* depth) {
     // the set epoch: the next one, or a cleared set (rmc_plan.h next_set_epoch)
     if (int rc = begin_set(c, !c->sh.verify)) return rc;
     if (int rc = reset_counters(c, false)) return rc;
+    if (cover_on(c))
+        if (int rc = cover_begin(c)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
@@ -417,6 +440,8 @@ static int start_run(rmc_ctx* c, int* depth) {
     if (int rc = read_counters(c)) return rc;
     *depth = seed_done(c);
     if (c->sh.verify) HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
+    if (cover_on(c))  // row Init: the one initial state generated, and what the seed stored
+        HIPCHK(c, launch_cover(c->sh, c->P, c->B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
     return 0;
 }
 
@@ -429,6 +454,8 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool resume = c->resume != 0;  // rmc_recover restored store, set and counters
     c->resume = 0;
     c->have_target = 0;
+    c->cov_valid = 0;
+    const bool cover = cover_on(c);  // (rmc_recover refuses the flag: never a resumed run)
     int depth = 0;
     if (resume) {
         c->res.left_on_queue = 0;
@@ -506,6 +533,8 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 if (want == 0) return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
                 b = a + want;
             }
+            // coverage reads Counters.count back after every launch, so it is current here
+            const u64 cov_before = c->h_ctr->count;
             HIPCHK(c, launch(c, Op::Expand, a, b));
             c->res.expand_launches += 1;
             if (c->sh.sym && !c->sh.verify) {
@@ -536,12 +565,25 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     c->res.spills = cnt / win;  // passes of the ring
                 }
             }
+            if (cover) {
+                // the coverage pass of this launch: its parents [a, b) are still resident
+                // (the store; the linear window, which moves only [base, a) and before the
+                // launch; the ring, whose room is relative to a), and the states it added
+                // are [count before, count after) — after k_ties, Publish / Verify
+                if (!c->sh.verify && !c->spill.on) {  // (those paths have read the counters)
+                    if (int rc = read_counters(c)) return rc;
+                    if (c->h_ctr->overflow || c->h_ctr->table_full) break;
+                }
+                HIPCHK(c, launch_cover(c->sh, c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+            }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
     }
     c->res.distinct = c->level_start.back();
     c->res.depth = depth;
     c->res.verified_spilled = c->spill.host_hits;
+    if (cover)
+        if (int rc = cover_end(c)) return rc;
     const double D = (double)c->res.distinct, G = (double)c->res.generated;
     // TLC's "calculated (optimistic)" fingerprint-collision estimate
     c->res.collision_probability = fp_collision_estimate(D, G, c->table_slots, c->set_epoch != 0);
@@ -566,6 +608,23 @@ int rmc_set_fp_bits(rmc_ctx* c, int32_t bits) {
     if (!c->sh.verify) return fail(c, RMC_E_INVAL, "rmc_set_fp_bits needs RMC_FLAG_VERIFY_STATES");
     c->P.fp_mask = bits == 64 ? ~0ull : ((1ull << bits) - 1);
     return 0;
+}
+
+int rmc_get_coverage(const rmc_ctx* c, rmc_coverage* out) {
+    if (!c || !out) return RMC_E_INVAL;
+    rmc_ctx* m = const_cast<rmc_ctx*>(c);  // (only the message is written)
+    if (!cover_on(c)) return fail(m, RMC_E_STATE, "rmc_get_coverage: the ctx was created without RMC_FLAG_COVERAGE");
+    if (!c->cov_valid) return fail(m, RMC_E_STATE, "rmc_get_coverage: no completed rmc_run_bfs to report");
+    *out = c->cov;
+    return 0;
+}
+
+const char* rmc_coverage_action(int32_t row) {
+    static const char* const kRows[RMC_COV_ACTIONS] = {
+        "Init", "Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest", "AdvanceCommitIndex",
+        "AppendEntries", "UpdateTerm", "Receive:RequestVoteRequest", "Receive:RequestVoteResponse",
+        "Receive:AppendEntriesRequest", "Receive:AppendEntriesResponse", "DuplicateMessage", "DropMessage"};
+    return row >= 0 && row < RMC_COV_ACTIONS ? kRows[row] : nullptr;
 }
 
 int rmc_get_result(const rmc_ctx* c, rmc_result* out) {

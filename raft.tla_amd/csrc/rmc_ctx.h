@@ -141,6 +141,12 @@ struct rmc_ctx {
     // single-GPU run takes the next epoch without clearing the set (rmc_run_bfs)
     rmc::u32 set_epoch = 0;
     rmc::u64 walked = 0;  // (state, lane) slots of the lane walk in the last run (RMC_WALK_STATS)
+    // action coverage (RMC_FLAG_COVERAGE; rmc_cover.h): the device tallies, generated[COV_ROWS]
+    // then distinct[COV_ROWS], allocated only with the flag (not part of Counters, whose size
+    // the sharded count rows fix), and the last completed run's copy (rmc_get_coverage)
+    unsigned long long* d_cov = nullptr;
+    rmc_coverage cov{};
+    int cov_valid = 0;
     rmc_result res{};
     std::string err;
     std::vector<rmc::u64> level_start;  // level d (1-based) = [level_start[d-1], level_start[d])
@@ -188,6 +194,11 @@ int read_counters(rmc_ctx* c);
 int begin_set(rmc_ctx* c, bool tagged);
 // Init (raft.tla:125-129), the one initial state: encoded, staged and seeded (k_seed).
 int seed_init(rmc_ctx* c);
+// Action coverage, both layouts: the tallies zeroed at the start of a run, and
+// copied out at its end (the stream is idle after it).
+inline bool cover_on(const rmc_ctx* c) { return (c->cfg.flags & RMC_FLAG_COVERAGE) != 0; }
+int cover_begin(rmc_ctx* c);
+int cover_end(rmc_ctx* c);
 // After the seed launch's read_counters, on either layout: level 1 is the states
 // it stored, and an invariant Init violates is the target.  Returns the depth.
 int seed_done(rmc_ctx* c);

@@ -655,6 +655,8 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
     if (!c || world < 1 || world > kMaxWorld || rank < 0 || rank >= world) return RMC_E_INVAL;
     if (!rccl_id && !(host && host->alltoallv && host->allgather))
         return fail(c, RMC_E_INVAL, "rmc_shard needs an RCCL id or a host transport");
+    if (c->cfg.flags & RMC_FLAG_COVERAGE)
+        return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_COVERAGE (coverage is single GPU)");
     if (c->spill.on) return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_SPILL");
     if (c->wide) return fail(c, RMC_E_INVAL, "sharded mode runs the packed layout only (bounds within its capacity)");
     HIPCHK(c, hipSetDevice(c->cfg.device));

@@ -132,6 +132,13 @@ struct SimCounters {
 hipError_t launch_sim(const Shape& sh, const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, u64 seed,
                       int mode, SimCounters* out, i64 rec_beh, u32* rec, hipStream_t st);
 
+// Action coverage (RMC_FLAG_COVERAGE): the pass beside one expansion launch over
+// the parents [lo, hi) — their enabled lanes into cov[0 .. COV_ROWS) by action
+// (rmc_cover.h) — and the states it added, [nlo, nhi), into cov[COV_ROWS .. 2 COV_ROWS)
+// by the action of their producing lane; n_init is added to row Init's generated.
+hipError_t launch_cover(const Shape& sh, const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi,
+                        u64 n_init, unsigned long long* cov, hipStream_t st);
+
 // Sharded mode, phase 1 owner side: insert n received keys (12-B {k lo, k hi, s32}
 // records), reply[t] = new;
 // keys [src_off[p], src_off[p + 1]) came from rank p, acc[p] += keys of p that were new.
@@ -218,6 +225,9 @@ struct WSucc {
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st);  // staged: B's work record (ring) / store record
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st);
 hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t st);  // the n deferred hits in B.vbuf
+// launch_cover on the wide records (k_wcover)
+hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
+                         unsigned long long* cov, hipStream_t st);
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,

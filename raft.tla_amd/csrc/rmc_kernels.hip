@@ -11,12 +11,16 @@
 //  k_seed   : inserts initial states (Init raft.tla:125-129) the same way.
 //  k_list   : the same lane code with every enabled successor written out
 //             (no dedup) — the differential-test entry point (rmc_expand).
+//  k_cover  : action coverage (RMC_FLAG_COVERAGE, TLC -coverage): a pass beside
+//             each expansion launch that tallies the enabled lanes of its
+//             parents and the producing lanes of its new states per action.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <map>
 #include <mutex>
 
 #include "raft_packed.h"
+#include "rmc_cover.h"
 #include "rmc_internal.h"
 #include "rmc_units.h"
 
@@ -1970,6 +1974,94 @@ __global__ __launch_bounds__(256) void k_list(const Params P, const PermTable PT
     }
 }
 
+// ---- action coverage (RMC_FLAG_COVERAGE, TLC -coverage; rmc_cover.h) ------------------
+// A pass of its own beside one expansion launch (the expansion kernels do not
+// change): `generated` over the launch's parents [lo, hi) — the lane walk of
+// k_list, every enabled lane tallied in its action's row — and `distinct` over
+// the states the launch added, [nlo, nhi): the row of each one's producing
+// lane (B.act), classified for a Receive lane from its parent's record, which
+// is still resident (the parent is of [lo, hi)).  n_init: initial states to
+// add to row Init's generated (the seed step).  Per-thread counts in registers
+// (every index a compile-time constant), a wave sum, one LDS add per wave and
+// row, one global atomic per block and non-zero row.
+__device__ __forceinline__ u32 wave_sum32(u32 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (u32)__shfl_xor((int)v, off);
+    return v;
+}
+
+template <int S, int K>
+__global__ __launch_bounds__(256) void k_cover(const Params P, const DevBufs B, u64 lo, u64 hi, u64 nlo, u64 nhi,
+                                               u64 n_init, unsigned long long* cov) {
+    constexpr int NW = 2 * S + K;
+    __shared__ u32 s_row[2 * COV_ROWS];
+    if (threadIdx.x < 2 * COV_ROWS) s_row[threadIdx.x] = 0;
+    __syncthreads();
+    u32 g[COV_ROWS], n[COV_ROWS];
+#pragma unroll
+    for (int r = 0; r < COV_ROWS; ++r) g[r] = n[r] = 0;
+    const u64 t0 = (u64)blockIdx.x * 256ull + threadIdx.x, step = (u64)gridDim.x * 256ull;
+    for (u64 i = lo + t0; i < hi; i += step) {
+        u64 w[S];
+        u32 m[K];
+        load_state<S, K>(B.store + wslot(B, i) * (u64)NW, w, m);
+        // one family at a time: its row is one value (Receive: per message), and
+        // the lane code is inlined once (lane_delta: a runtime lane, wave-uniform here)
+#pragma unroll 1
+        for (int f = 0; f < 10; ++f) {
+            u32 on = 0;
+#pragma unroll 1
+            for (int lane = P.off[f]; lane < P.off[f + 1]; ++lane) {
+                Delta d;
+                lane_delta<S, K>(w, m, lane, P, d);
+                if (!d.en) continue;
+                if (f == 7) {
+                    const int row = cover_row<S, K>(P, w, m, lane);
+#pragma unroll
+                    for (int r = COV_UPDATE_TERM; r < COV_DUPLICATE; ++r) g[r] += row == r ? 1u : 0u;
+                } else {
+                    ++on;
+                }
+            }
+            const int frow = f == 7 ? -1 : cover_family_row(f);
+#pragma unroll
+            for (int r = 0; r < COV_ROWS; ++r) g[r] += frow == r ? on : 0u;  // (g's indices stay constants)
+        }
+    }
+    nhi = nhi < B.cap ? nhi : B.cap;  // (a launch that overflowed the store is an error: its tallies are not read)
+    for (u64 i = nlo + t0; i < nhi; i += step) {
+        const int lane = (int)B.act[i];
+        int row = COV_INIT;  // 255: an initial state
+        if (lane != 255) {
+            if (lane >= P.off[10]) continue;
+            const int f = lane_family(P, lane);
+            row = f == 7 ? -1 : cover_family_row(f);
+            if (f == 7) {
+                const u64 p = B.parent[i];
+                if (p < lo || p >= hi) continue;  // not of this launch: left out, and the sums show it
+                u64 w[S];
+                u32 m[K];
+                load_state<S, K>(B.store + wslot(B, p) * (u64)NW, w, m);
+                row = cover_row<S, K>(P, w, m, lane);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < COV_ROWS; ++r) n[r] += row == r ? 1u : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < COV_ROWS; ++r) {
+        const u32 gs = wave_sum32(g[r]), ns = wave_sum32(n[r]);
+        if (__lane_id() == 0 && gs) atomicAdd(&s_row[r], gs);
+        if (__lane_id() == 0 && ns) atomicAdd(&s_row[COV_ROWS + r], ns);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * COV_ROWS) {
+        u64 v = s_row[threadIdx.x];
+        if (threadIdx.x == COV_INIT && blockIdx.x == 0) v += n_init;
+        if (v) atomicAdd(&cov[threadIdx.x], (unsigned long long)v);
+    }
+}
+
 // ---- simulation (TLC -simulate; Smokeraft.cfg) -------------
 // One thread per behaviour: a random initial state from `inits`, then up to
 // depth-1 steps, each choosing uniformly (one reservoir pass over the lanes)
@@ -2050,6 +2142,17 @@ static hipError_t launch_sim_t(const Params& P, const u32* inits, u64 n_init, u6
     const u64 g = blocks < 4096 ? blocks : 4096;
     hipLaunchKernelGGL((k_simulate<S, K>), dim3((unsigned)g), dim3(256), 0, st, P, inits, n_init, n_beh, depth, seed,
                        mode, out, rec_beh, rec);
+    return hipGetLastError();
+}
+
+// The coverage pass of one expansion launch (or of the seed step: no parents).
+template <int S, int K>
+static hipError_t launch_cover_t(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
+                                 unsigned long long* cov, hipStream_t st) {
+    const u64 np = hi > lo ? hi - lo : 0, nn = nhi > nlo ? nhi - nlo : 0;
+    const u64 blocks = ((np > nn ? np : nn) + 255) / 256;
+    const u64 g = blocks < 1 ? 1 : blocks < 2048 ? blocks : 2048;  // grid-stride over both ranges
+    hipLaunchKernelGGL((k_cover<S, K>), dim3((unsigned)g), dim3(256), 0, st, P, B, lo, hi, nlo, nhi, n_init, cov);
     return hipGetLastError();
 }
 
@@ -2221,6 +2324,8 @@ static hipError_t launch_sk(bool sym, bool verify, Op op, const Params& P, const
     hipError_t launch_sim_shape_##SS##_##KK(const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, \
                                             u64 seed, int mode, SimCounters* out, i64 rec_beh, u32* rec,        \
                                             hipStream_t st);                                                    \
+    hipError_t launch_cover_shape_##SS##_##KK(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo,       \
+                                              u64 nhi, u64 n_init, unsigned long long* cov, hipStream_t st);    \
     hipError_t set_fp_salt_shape_##SS##_##KK(u64 salt, u64 ep, hipStream_t st);
 RMC_SHAPES(RMC_SHAPE_DECLS)
 
@@ -2235,6 +2340,10 @@ RMC_SHAPES(RMC_SHAPE_DECLS)
                                             u64 seed, int mode, SimCounters* out, i64 rec_beh, u32* rec,        \
                                             hipStream_t st) {                                                   \
         return launch_sim_t<SS, KK>(P, inits, n_init, n_beh, depth, seed, mode, out, rec_beh, rec, st);        \
+    }                                                                                                           \
+    hipError_t launch_cover_shape_##SS##_##KK(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo,       \
+                                              u64 nhi, u64 n_init, unsigned long long* cov, hipStream_t st) {   \
+        return launch_cover_t<SS, KK>(P, B, lo, hi, nlo, nhi, n_init, cov, st);                                \
     }                                                                                                           \
     hipError_t set_fp_salt_shape_##SS##_##KK(u64 salt, u64 ep, hipStream_t st) {                                \
         /* staged on this call's stack and waited for: concurrent callers (one host */                          \
@@ -2285,6 +2394,15 @@ hipError_t launch_sim(const Shape& sh, const Params& P, const u32* inits, u64 n_
         return launch_sim_shape_##SS##_##KK(P, inits, n_init, n_beh, depth, seed, mode, out, rec_beh, rec, st);
     RMC_SHAPES(RMC_SCASE)
 #undef RMC_SCASE
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_cover(const Shape& sh, const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi,
+                        u64 n_init, unsigned long long* cov, hipStream_t st) {
+#define RMC_CCASE(SS, KK) \
+    if (sh.S == SS && sh.K == KK) return launch_cover_shape_##SS##_##KK(P, B, lo, hi, nlo, nhi, n_init, cov, st);
+    RMC_SHAPES(RMC_CCASE)
+#undef RMC_CCASE
     return hipErrorInvalidValue;
 }
 #endif  // RMC_SHAPE_S

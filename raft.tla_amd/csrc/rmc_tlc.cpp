@@ -122,8 +122,19 @@ const char* inv_name(int bit) {
 // the message's term is newer, else the one for its mtype).
 std::string g_override_header;  // an override's action location (front-end notes), e.g. BugBecomeLeader
 
+// `<shown line L1, col C1 to line L2, col C2 of module raft>` for an action key
+// of rmc_action_location, `<shown>` when it has no location.
+std::string action_header(const std::string& action, const std::string& shown) {
+    if (action == "BecomeLeader" && !g_override_header.empty()) return g_override_header;
+    int32_t loc[4];
+    if (rmc_action_location(action.c_str(), loc) != 0) return "<" + shown + ">";
+    char buf[256];
+    snprintf(buf, sizeof buf, "<%s line %d, col %d to line %d, col %d of module raft>", shown.c_str(), loc[0], loc[1],
+             loc[2], loc[3]);
+    return buf;
+}
+
 std::string step_header(int family, int instance, const rmc_state_view& parent) {
-    if (family == 3 && !g_override_header.empty()) return g_override_header;
     std::string action = kFamilies[family], shown = action;
     if (family == 7) {
         const int S = parent.n_servers;
@@ -134,12 +145,20 @@ std::string step_header(int family, int instance, const rmc_state_view& parent) 
             else action = std::string("Receive:") + kMtypes[m.mtype];
         }
     }
-    int32_t loc[4];
-    if (rmc_action_location(action.c_str(), loc) != 0) return "<" + shown + ">";
-    char buf[256];
-    snprintf(buf, sizeof buf, "<%s line %d, col %d to line %d, col %d of module raft>", shown.c_str(), loc[0], loc[1],
-             loc[2], loc[3]);
-    return buf;
+    return action_header(action, shown);
+}
+
+// TLC -coverage: one line per action of Next (and Init), `<header>: distinct:generated`,
+// the headers those of the trace printer (a Receive disjunct is shown as Receive).
+void print_coverage(const rmc_coverage& cv) {
+    printf("The coverage statistics :\n");
+    for (int row = 0; row < RMC_COV_ACTIONS; ++row) {
+        const std::string action = rmc_coverage_action(row);
+        const std::string shown = action.compare(0, 8, "Receive:") == 0 ? "Receive" : action;
+        printf("%s: %llu:%llu\n", action_header(action, shown).c_str(), (unsigned long long)cv.distinct[row],
+               (unsigned long long)cv.generated[row]);
+    }
+    printf("End of statistics.\n");
 }
 
 int progress(const rmc_level_stats* s, void*) {
@@ -154,7 +173,12 @@ int usage() {
     fprintf(stderr,
             "usage: rmc-tlc [-config X.cfg] [-depth N] [-deadlock] [-device D] [-capacity N] [-workers N]\n"
             "               [-verify] [-fpseed S] [-checkpoint F] [-recover F] [-simulate [num=N]] [-seed S]\n"
-            "               [-raft raft.tla] [-builtin-raft] [-gpus N] [-nospill] [-window N] [-fpmem B] X.tla\n"
+            "               [-raft raft.tla] [-builtin-raft] [-gpus N] [-nospill] [-window N] [-fpmem B]\n"
+            "               [-coverage [minutes]] X.tla\n"
+            "  -coverage [M]  per-action statistics (TLC -coverage): for every action of Next the states it\n"
+            "             generated and the distinct states it found; M, TLC's reporting interval in\n"
+            "             minutes, is accepted and ignored (single GPU; not with -checkpoint, -recover\n"
+            "             or -simulate)\n"
             "  -gpus N        shard the search over N GPUs (one ctx and RCCL rank per GPU)\n"
             "  -raft F        the raft.tla to verify against the compiled-in spec (default: next to X.tla)\n"
             "  -builtin-raft  no raft.tla on disk: check the compiled-in lemmy/raft.tla (said in the output)\n"
@@ -245,7 +269,7 @@ int main(int argc, char** argv) {
     std::string ckpt, recover, raft;
     uint32_t fopts = 0;
     unsigned long long capacity = 0, window = 0, fpmem = 0;
-    int nospill = 0;
+    int nospill = 0, coverage = 0;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : nullptr; };
@@ -258,6 +282,12 @@ int main(int argc, char** argv) {
         else if (s == "-gpus") { const char* v = next(); if (!v) return usage(); gpus = atoi(v); }
         else if (s == "-verify") verify = 1;
         else if (s == "-nospill") nospill = 1;
+        else if (s == "-coverage") {  // TLC's optional interval in minutes: a number, not the model
+            coverage = 1;
+            if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9' &&
+                strspn(argv[a + 1], "0123456789") == strlen(argv[a + 1]))
+                ++a;
+        }
         else if (s == "-fpmem") {
             const char* v = next();
             if (!v) return usage();
@@ -283,6 +313,11 @@ int main(int argc, char** argv) {
         else tla = s;
     }
     if (tla.empty()) return usage();
+    if (coverage && (gpus > 1 || !ckpt.empty() || !recover.empty() || simulate)) {
+        fprintf(stderr, "-coverage counts whole single-GPU searches: not with %s\n",
+                gpus > 1 ? "-gpus N > 1" : !ckpt.empty() ? "-checkpoint" : !recover.empty() ? "-recover" : "-simulate");
+        return usage();
+    }
     if (cfg.empty()) cfg = (tla.size() > 4 && tla.substr(tla.size() - 4) == ".tla" ? tla.substr(0, tla.size() - 4) : tla) + ".cfg";
     printf("rmc-tlc: %s\n", rmc_version());
     if (const char* b = getenv("RMC_BUILTIN_RAFT")) if (b[0] == '1') fopts |= RMC_FRONT_BUILTIN_RAFT;
@@ -303,6 +338,7 @@ int main(int argc, char** argv) {
     c.state_capacity = capacity;
     if (nodeadlock) c.flags &= ~RMC_FLAG_CHECK_DEADLOCK;
     if (verify) c.flags |= RMC_FLAG_VERIFY_STATES;
+    if (coverage) c.flags |= RMC_FLAG_COVERAGE;
     // like TLC's states/ directory, expanded levels leave the device when it fills
     // (single GPU; under -verify the spilled states keep a host copy for the
     // comparisons, and checkpoints of such runs stay resident).  The wide layout of
@@ -438,6 +474,11 @@ int main(int argc, char** argv) {
         if (r.verified_spilled)
             printf("  (%llu of the hits were on states that had left the device window: compared with "
                    "their host copies)\n", (unsigned long long)r.verified_spilled);
+    }
+    if (coverage) {
+        rmc_coverage cv;
+        if (rmc_get_coverage(ctx, &cv)) printf("Error: %s\n", rmc_last_error(ctx));
+        else print_coverage(cv);
     }
     printf("%llu states generated, %llu distinct states found, %llu states left on queue.\n",
            (unsigned long long)r.generated, (unsigned long long)r.distinct, (unsigned long long)r.left_on_queue);

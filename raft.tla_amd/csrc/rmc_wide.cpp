@@ -217,6 +217,9 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     }
     c->h_ctr->count = 0;
     if (int rc = reset_counters(c, false)) return rc;
+    const bool cover = cover_on(c);
+    if (cover)
+        if (int rc = cover_begin(c)) return rc;
     // Init in the record the seed kernel reads: the work record (= the store's without the ring)
     HIPCHK(c, with_record(B.window ? B.work : B.compact, [&](auto* r) {
         std::remove_pointer_t<decltype(r)> init;
@@ -227,6 +230,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     HIPCHK(c, launch_wseed(c->WM, B, c->w_staged, 1, c->st));
     if (int rc = read_counters(c)) return rc;
     int depth = seed_done(c);
+    if (cover)  // row Init: the one initial state generated, and what the seed stored
+        HIPCHK(c, launch_wcover(c->WM, B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
     const u64 CHUNK = 1ull << 22;
     const u64 bound = wide_new_per_state(c->cfg, B.work);
     u64 records = c->h_ctr->count;  // ring: records written so far
@@ -256,7 +261,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 if (want == 0) return window_too_small(c, B.window, 8);
                 b = a + want;
             }
-            B.vbase = c->h_ctr->count;  // (verification: read back after every launch)
+            B.vbase = c->h_ctr->count;  // (verification, coverage: read back after every launch)
+            const u64 cov_before = c->h_ctr->count;
             HIPCHK(c, launch_wexpand(c->WM, B, a, b, c->st));
             c->res.expand_launches += 1;
             if (B.verify) {
@@ -284,12 +290,24 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 c->res.spilled = records > B.window ? records - B.window : 0;
                 c->res.spills = records / B.window;  // passes of the ring
             }
+            if (cover) {
+                // the coverage pass of this launch: the ring still holds its parents [a, b)
+                // (its room is relative to a), and the states it added, [count before, count
+                // after), have their links even on the unstored last level
+                if (!B.verify && !B.window) {  // (those paths have read the counters)
+                    if (int rc = read_counters(c)) return rc;
+                    if (c->h_ctr->overflow || c->h_ctr->table_full) break;
+                }
+                HIPCHK(c, launch_wcover(c->WM, B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+            }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
     }
     c->res.distinct = c->level_start.back();
     c->res.depth = depth;
     c->res.stored_here = c->res.distinct;
+    if (cover)
+        if (int rc = cover_end(c)) return rc;
     const double Dd = (double)c->res.distinct, G = (double)c->res.generated;
     c->res.collision_probability = fp_collision_estimate(Dd, G, (c->WB.tmask + 1));
     c->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

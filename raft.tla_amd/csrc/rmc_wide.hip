@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "raft_wide.h"
+#include "rmc_cover.h"
 #include "rmc_internal.h"
 
 namespace rmc {
@@ -227,6 +228,86 @@ __global__ __launch_bounds__(256) void k_wverify(const WModel M, const WideBufs 
     vcol = w_wave_sum(vcol);
     if (__lane_id() == 0 && vchk) atomicAdd((unsigned long long*)&B.ctr->vchecked, (unsigned long long)vchk);
     if (__lane_id() == 0 && vcol) atomicAdd((unsigned long long*)&B.ctr->collisions, (unsigned long long)vcol);
+}
+
+// Action coverage (RMC_FLAG_COVERAGE; rmc_cover.h, the packed k_cover's twin): a
+// pass of its own beside one expansion launch over [lo, hi).  `generated`: the
+// expansion's lane walk — families 0-6, then the bag families over the state's
+// messages — with only the guards evaluated on the stored record (wlane without
+// a successor: anything but W_OFF counts, as in k_wexpand).  `distinct`: the
+// states the launch added, [nlo, nhi), by the row of their producing lane; a
+// Receive lane reads its parent's record, which the ring still holds (ring_room
+// is relative to lo), and a state of the unstored last level has its links.
+__device__ __forceinline__ u32 w_wave_sum32(u32 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (u32)__shfl_xor((int)v, off);
+    return v;
+}
+
+template <class Store, bool Ring>
+__global__ __launch_bounds__(256) void k_wcover(const WModel M, const WideBufs B, u64 lo, u64 hi, u64 nlo, u64 nhi,
+                                                u64 n_init, unsigned long long* cov) {
+    __shared__ u32 s_row[2 * COV_ROWS];
+    if (threadIdx.x < 2 * COV_ROWS) s_row[threadIdx.x] = 0;
+    __syncthreads();
+    u32 g[COV_ROWS], n[COV_ROWS];
+#pragma unroll
+    for (int r = 0; r < COV_ROWS; ++r) g[r] = n[r] = 0;
+    const Store* store = static_cast<const Store*>(B.store);
+    const u64 t0 = (u64)blockIdx.x * 256ull + threadIdx.x, step = (u64)gridDim.x * 256ull;
+    for (u64 i = lo + t0; i < hi; i += step) {
+        const Store& s = store[w_slot<Ring>(B, i)];
+        const int nb = s.nmsg;
+#pragma unroll 1
+        for (int f = 0; f < 10; ++f) {  // one family at a time: its row is one value (Receive: per message)
+            u32 on = 0;
+            const int l0 = M.L.off[f], l1 = f < 7 ? M.L.off[f + 1] : l0 + nb;
+#pragma unroll 1
+            for (int lane = l0; lane < l1; ++lane) {
+                if (wlane(M, s, lane, nullptr) == W_OFF) continue;
+                if (f == 7) {
+                    const int row = wcover_row(M, s, lane);
+#pragma unroll
+                    for (int r = COV_UPDATE_TERM; r < COV_DUPLICATE; ++r) g[r] += row == r ? 1u : 0u;
+                } else {
+                    ++on;
+                }
+            }
+            const int frow = f == 7 ? -1 : cover_family_row(f);
+#pragma unroll
+            for (int r = 0; r < COV_ROWS; ++r) g[r] += frow == r ? on : 0u;  // (g's indices stay constants)
+        }
+    }
+    nhi = nhi < B.cap ? nhi : B.cap;  // (a launch that overflowed the store is an error: its tallies are not read)
+    for (u64 i = nlo + t0; i < nhi; i += step) {
+        const int lane = (int)B.act[i];
+        int row = COV_INIT;  // 255: an initial state
+        if (lane != 255) {
+            const int f = M.L.family(lane);
+            row = f == 7 ? -1 : cover_family_row(f);
+            if (f == 7) {
+                const u64 p = B.parent[i];
+                if (p < lo || p >= hi) continue;  // not of this launch: left out, and the sums show it
+                const Store& s = store[w_slot<Ring>(B, p)];
+                if (lane - M.L.off[7] >= (int)s.nmsg) continue;
+                row = wcover_row(M, s, lane);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < COV_ROWS; ++r) n[r] += row == r ? 1u : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < COV_ROWS; ++r) {
+        const u32 gs = w_wave_sum32(g[r]), ns = w_wave_sum32(n[r]);
+        if (__lane_id() == 0 && gs) atomicAdd(&s_row[r], gs);
+        if (__lane_id() == 0 && ns) atomicAdd(&s_row[COV_ROWS + r], ns);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * COV_ROWS) {
+        u64 v = s_row[threadIdx.x];
+        if (threadIdx.x == COV_INIT && blockIdx.x == 0) v += n_init;
+        if (v) atomicAdd(&cov[threadIdx.x], (unsigned long long)v);
+    }
 }
 
 // Every enabled lane of n given states, without dedup (rmc_expand).
@@ -622,6 +703,18 @@ hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t
     else if (B.compact) hipLaunchKernelGGL(k_wverify<WStateC>, grid, dim3(256), 0, st, M, B, n);
     else hipLaunchKernelGGL(k_wverify<WState>, grid, dim3(256), 0, st, M, B, n);
     return hipGetLastError();
+}
+hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
+                         unsigned long long* cov, hipStream_t st) {
+    const u64 np = hi > lo ? hi - lo : 0, nn = nhi > nlo ? nhi - nlo : 0;
+    const dim3 grid(grid_for(np > nn ? np : nn, 256, 4096));
+    // the store's record on both sides: the guards read it in place (no work record)
+    const bool ok = w_dispatch(B, [&](auto* sp, auto*, auto ring) {
+        typedef std::remove_pointer_t<decltype(sp)> Store;
+        constexpr bool Ring = decltype(ring)::value;
+        hipLaunchKernelGGL((k_wcover<Store, Ring>), grid, dim3(256), 0, st, M, B, lo, hi, nlo, nhi, n_init, cov);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st) {

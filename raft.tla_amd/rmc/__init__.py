@@ -33,6 +33,13 @@ INV_NAMES = {INV_TYPEOK: "TypeOK", INV_ONE_LEADER: "OneLeaderPerTerm",
              INV_MORE_UP_TO_DATE: "MoreUpToDateCorrect", INV_LEADER_COMPLETE: "LeaderCompleteness"}
 FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED = 1, 2, 4
 FLAG_UNBOUNDED_TERM, FLAG_UNBOUNDED_LOG, FLAG_UNBOUNDED_MSGS, FLAG_UNBOUNDED_DUP = 32, 64, 128, 256
+FLAG_COVERAGE = 512
+# rows of rmc_coverage (RMC_COV_ACTIONS; rmc_coverage_action): Init, the server families, the
+# disjuncts of Receive, DuplicateMessage, DropMessage
+COVERAGE_ACTIONS = ("Init", "Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
+                    "AdvanceCommitIndex", "AppendEntries", "UpdateTerm", "Receive:RequestVoteRequest",
+                    "Receive:RequestVoteResponse", "Receive:AppendEntriesRequest",
+                    "Receive:AppendEntriesResponse", "DuplicateMessage", "DropMessage")
 FAMILIES = ("Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
             "AdvanceCommitIndex", "AppendEntries", "Receive", "DuplicateMessage",
             "DropMessage")
@@ -118,6 +125,11 @@ ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 
 
+class Coverage(C.Structure):
+    _fields_ = [("generated", C.c_uint64 * len(COVERAGE_ACTIONS)),
+                ("distinct", C.c_uint64 * len(COVERAGE_ACTIONS))]
+
+
 class Transport(C.Structure):
     _fields_ = [("user", C.c_void_p), ("alltoallv", ALLTOALLV_FN), ("allgather", ALLGATHER_FN)]
 
@@ -127,7 +139,7 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_config_from_files", "rmc_probe_bench", "rmc_rccl_unique_id", "rmc_shard",
            "rmc_set_seed", "rmc_simulate", "rmc_sim_replay", "rmc_set_fp_bits",
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
-           "rmc_action_location", "rmc_smoke_init")
+           "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action")
 
 _lib = None
 
@@ -195,6 +207,10 @@ def native():
         lib.rmc_sim_replay.argtypes = [C.c_void_p, C.POINTER(SimConfig), C.c_uint64,
                                        C.POINTER(StateView), C.c_size_t, C.POINTER(C.c_size_t)]
         lib.rmc_sim_replay.restype = C.c_int
+        lib.rmc_get_coverage.argtypes = [C.c_void_p, C.POINTER(Coverage)]
+        lib.rmc_get_coverage.restype = C.c_int
+        lib.rmc_coverage_action.argtypes = [C.c_int32]
+        lib.rmc_coverage_action.restype = C.c_char_p
         _lib = lib
     return _lib
 
@@ -208,10 +224,10 @@ class RmcError(RuntimeError):
 def make_config(n_servers=3, n_values=2, max_term=2, max_log_len=1, max_msgs=2, max_dup=1,
                 symmetry=False, bug_quorum=False, invariants=INV_TYPEOK, check_deadlock=True,
                 device=0, max_depth=0, state_capacity=0, verify_states=False, spill=False, device_window=0,
-                set_bytes=0):
+                set_bytes=0, coverage=False):
     flags = (FLAG_SYMMETRY if symmetry else 0) | (FLAG_BUG_QUORUM if bug_quorum else 0) | \
         (FLAG_CHECK_DEADLOCK if check_deadlock else 0) | (FLAG_VERIFY_STATES if verify_states else 0) | \
-        (FLAG_SPILL if spill else 0)
+        (FLAG_SPILL if spill else 0) | (FLAG_COVERAGE if coverage else 0)
     return Config(n_servers, n_values, max_term, max_log_len, max_msgs, max_dup, flags,
                   invariants, device, max_depth, state_capacity, 0, device_window, set_bytes)
 
@@ -375,6 +391,13 @@ class Checker:
     def set_seed(self, seed: int):
         """Fingerprint salt for the next run (rmc_set_seed)."""
         self._check(self.lib.rmc_set_seed(self.ctx, seed))
+
+    def coverage(self):
+        """rmc_get_coverage after a run() on a ctx made with coverage=True:
+        {action: (generated, distinct)} in the order of COVERAGE_ACTIONS."""
+        cv = Coverage()
+        self._check(self.lib.rmc_get_coverage(self.ctx, C.byref(cv)))
+        return {a: (cv.generated[k], cv.distinct[k]) for k, a in enumerate(COVERAGE_ACTIONS)}
 
     def result(self) -> Result:
         res = Result()

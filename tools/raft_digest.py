@@ -245,7 +245,7 @@ def main():
     spans = []
     for a in ("Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
               "AdvanceCommitIndex", "AppendEntries", "DuplicateMessage", "DropMessage",
-              "UpdateTerm"):
+              "UpdateTerm", "Init"):
         spans.append((a, *body_span(defs[a])))
     rs = receive_spans(defs["Receive"])
     assert len(rs) == 5, rs

@@ -24,9 +24,9 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 9 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
-                             rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
-                             rmc_coverage_action (round 8) */
+#define RMC_ABI_VERSION 10 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+                              rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
+                              rmc_coverage_action (round 8); 10: rmc_check_states */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -117,7 +117,18 @@ extern "C" {
                                            /* layouts; no checkpoint / recover; ignored by */
                                            /* rmc_simulate                                 */
 
-/* rmc_config.invariants — the INVARIANT names the engine knows (fused checks). */
+/* rmc_config.invariants — the INVARIANT names the engine knows (fused checks).
+ * TypeOK on the packed layout: the search (rmc_run_bfs, rmc_simulate) evaluates
+ * every conjunct a packed state can violate except two, which it takes by
+ * induction from Init (or from SmokeInit's draws): the entry values inside
+ * messages, m.mentries of an AppendEntriesRequest (raft.tla:456) and m.mlog of a
+ * RequestVoteResponse (:465), in Seq([term : Nat, value : Value]).  A message's
+ * entries are copied from a log (raft.tla:183, :259), a log's entries come from
+ * ClientRequest (v \in Value) or from a message (:330), and the logs' values are
+ * checked, so no state reached from Init violates them.  (nextIndex >= 1 holds
+ * by construction of the packed word: it is stored minus one.)  rmc_check_states,
+ * whose states come from the caller, evaluates the complete predicate, these two
+ * conjuncts included; the wide layout evaluates it everywhere. */
 #define RMC_INV_TYPEOK (1u << 0)           /* raft.tla:482-492                          */
 #define RMC_INV_ONE_LEADER (1u << 1)       /* ElectionSafety restated (raft.tla:1124)   */
 #define RMC_INV_LOG_MATCHING (1u << 2)     /* raft.tla:1132-1136                        */
@@ -358,6 +369,18 @@ int rmc_recover(rmc_ctx* ctx, const char* path);
 size_t rmc_state_bytes(const rmc_config* cfg);
 int rmc_expand(rmc_ctx* ctx, const rmc_state_view* states, size_t n, rmc_succ_view* out,
                size_t cap, size_t* n_out);
+/* Test hook: evaluate the SAME device invariant code as the BFS / simulator on n
+ * caller states.  invariants = RMC_INV_* mask for this call (0 = the ctx's own).
+ * violated[t] = 0, or the RMC_INV_* bit of the first violated invariant of state
+ * t (the notion of rmc_result.violated_inv: the lowest bit of the mask that
+ * fails).  The states need not be reachable, nor within the CONSTRAINT; a view
+ * the layout's encoder refuses, a mask bit above RMC_INV_LEADER_COMPLETE or a
+ * NULL array with n > 0 is RMC_E_INVAL with the reason; n = 0 launches nothing.
+ * On the wide layout RMC_WSIM (read at each call) picks the check as it picks
+ * the simulation kernel: 1 (default) the one-wave-per-state check, 0 the
+ * one-thread-per-state check the BFS uses. */
+int rmc_check_states(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint32_t invariants,
+                     int32_t* violated);
 
 /* ---- simulation (TLC -simulate; Smokeraft.cfg, config 4) ---------------------
  * Replaces TLC's Simulator: random behaviours, each from a random initial state

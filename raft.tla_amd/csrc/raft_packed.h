@@ -1032,6 +1032,35 @@ RMC_HD int type_ok(const u64 (&w)[S], const u32 (&m)[K], int V) {  // raft.tla:4
         const u32 sl = m[q];
         if (!sl) continue;
         if (m_src(sl) >= (u32)S || m_dst(sl) >= (u32)S) return 0;
+        // the entry values inside messages hold by induction from Init (msg_entries_ok)
+    }
+    return 1;
+}
+// The conjuncts of TypeOK that type_ok leaves out: the entry values inside
+// messages, mentries of an AppendEntriesRequest (raft.tla:456) and mlog of a
+// RequestVoteResponse (:465) in Seq([term : Nat, value : Value]).  From Init
+// (no messages) they hold by induction: a message's entries are copied from a
+// log (AppendEntries :183, the vote reply :259), a log's entries come from
+// ClientRequest (v \in Value, :206-211) or from a message (:330), and type_ok
+// checks the logs.  So the BFS kernels, whose states all descend from Init, and
+// k_simulate, whose walks start at Init or at SmokeInit's draws (entry values
+// drawn from Value: rmc_codec.cpp), check type_ok alone — inlined into every
+// expansion kernel, these conjuncts cost SGPR spills there (DESIGN.md "Named
+// invariants") — and the complete predicate, type_ok && msg_entries_ok, is
+// check_invariants<S, K, true>: rmc_check_states, whose states come from the
+// caller.  A value is one bit, so with |Value| = VMAX every encodable value is
+// in Value.
+template <int K>
+RMC_HD int msg_entries_ok(const u32 (&m)[K], int V) {
+    if (V >= VMAX) return 1;
+    for (int q = 0; q < K; ++q) {
+        const u32 sl = m[q];
+        if (!sl) continue;
+        const u32 ty = m_type(sl);
+        if (ty == AEQ && ((sl >> 19) & 1u) && ((sl >> 24) & 1u) >= (u32)V) return 0;  // mentries[1]: entry at bits 20-24
+        if (ty == RVP)  // mlog: Len at bits 13-14, entry x at bits 15 + 5 x
+            for (u32 x = 0; x < ((sl >> 13) & 3u); ++x)
+                if (((sl >> (15 + ENT_W * (int)x + 4)) & 1u) >= (u32)V) return 0;
     }
     return 1;
 }
@@ -1191,10 +1220,14 @@ RMC_HD_COLD int check_named_invariants(const PackedState<S, K> s, int mask) {
     if ((mask & 512) && !leader_completeness<S>(s.w)) return 10;
     return 0;
 }
-// 0 = all hold, else 1 + index of the first violated invariant bit.
-template <int S, int K>
+// 0 = all hold, else 1 + index of the first violated invariant bit.  COMPLETE:
+// TypeOK with the conjuncts the states reached from Init satisfy by induction
+// (msg_entries_ok), for states that come from a caller.
+template <int S, int K, bool COMPLETE = false>
 RMC_HD int check_invariants(const u64 (&w)[S], const u32 (&m)[K], const Params& P) {
     if ((P.inv_mask & 1) && !type_ok<S, K>(w, m, P.V)) return 1;
+    if constexpr (COMPLETE)
+        if ((P.inv_mask & 1) && !msg_entries_ok<K>(m, P.V)) return 1;
     if (P.inv_mask & ~1) {
         PackedState<S, K> s;
         for (int i = 0; i < S; ++i) s.w[i] = w[i];

@@ -867,4 +867,33 @@ int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view
     return 0;
 }
 
+int rmc_check_states(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t invariants, int32_t* violated) {
+    if (!c) return RMC_E_INVAL;
+    if (n && (!states || !violated)) return fail(c, RMC_E_INVAL, "rmc_check_states: states or violated is NULL");
+    if (invariants & ~1023u) return fail(c, RMC_E_INVAL, "rmc_check_states: unknown invariant bit");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n == 0) return 0;
+    const uint32_t mask = invariants ? invariants : c->cfg.invariants;
+    if (c->wide) return check_wide(c, states, n, mask, violated);
+    const int NW = c->NW;
+    std::vector<u32> packed(n * (size_t)NW);
+    std::string why;
+    for (size_t t = 0; t < n; ++t)
+        if (encode_view(c->sh.S, c->sh.K, states[t], packed.data() + t * NW, &why))
+            return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
+    Params P = c->P;
+    P.inv_mask = (int)mask;
+    DevScratch<u32> d_in;
+    DevScratch<int> d_out;
+    HIPCHK(c, d_in.alloc(packed.size()));
+    HIPCHK(c, d_out.alloc(n));
+    HIPCHK(c, hipMemcpy(d_in.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, launch_check(c->sh, P, d_in.get(), (u64)n, d_out.get(), c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    std::vector<int> v(n);
+    HIPCHK(c, hipMemcpy(v.data(), d_out.get(), n * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < n; ++t) violated[t] = v[t] ? 1 << (v[t] - 1) : 0;
+    return 0;
+}
+
 }  // extern "C"

@@ -254,6 +254,7 @@ void destroy_wide(rmc_ctx* c);
 int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user);
 int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap, size_t* len);
 int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view* out, size_t cap, size_t* n_out);
+int check_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t mask, int32_t* violated);
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, rmc::i64 rec_beh,
              std::vector<rmc_state_view>* rec);
 void fill_wide_model(rmc_ctx* c);

@@ -132,6 +132,10 @@ struct SimCounters {
 hipError_t launch_sim(const Shape& sh, const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, u64 seed,
                       int mode, SimCounters* out, i64 rec_beh, u32* rec, hipStream_t st);
 
+// rmc_check_states: out[t] = check_invariants (0, or 1 + the bit index of the first violated
+// invariant of P.inv_mask) of caller state t of `in` (n packed states of the shape).
+hipError_t launch_check(const Shape& sh, const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
+
 // Action coverage (RMC_FLAG_COVERAGE): the pass beside one expansion launch over
 // the parents [lo, hi) — their enabled lanes into cov[0 .. COV_ROWS) by action
 // (rmc_cover.h) — and the states it added, [nlo, nhi), into cov[COV_ROWS .. 2 COV_ROWS)
@@ -232,6 +236,10 @@ hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u6
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,
                             SimCounters* out, i64 rec_beh, WState* rec, hipStream_t st);
+// rmc_check_states on the wide layout: out[t] = the invariant result of M.inv_mask on in[t], by
+// wcheck_invariants with one thread per state (wave = 0: the BFS's and k_wsimulate's check), or by
+// w_check_invariants_wave with one wave per state on a copy in LDS (k_wsimulate_w's)
+hipError_t launch_wcheck(const WModel& M, const WState* in, u64 n, int* out, int wave, hipStream_t st);
 }  // namespace wide
 
 }  // namespace rmc

@@ -1974,6 +1974,20 @@ __global__ __launch_bounds__(256) void k_list(const Params P, const PermTable PT
     }
 }
 
+// The invariants of n given states, one thread per state (rmc_check_states): the
+// expansion kernels' and k_simulate's check_invariants and nothing else, with the
+// complete TypeOK (raft_packed.h msg_entries_ok: the states are the caller's).
+template <int S, int K>
+__global__ __launch_bounds__(256) void k_check(const Params P, const u32* in, u64 n, int* out) {
+    constexpr int NW = 2 * S + K;
+    const u64 t = (u64)blockIdx.x * 256ull + threadIdx.x;
+    if (t >= n) return;
+    u64 w[S];
+    u32 m[K];
+    load_state<S, K>(in + t * (u64)NW, w, m);
+    out[t] = check_invariants<S, K, true>(w, m, P);
+}
+
 // ---- action coverage (RMC_FLAG_COVERAGE, TLC -coverage; rmc_cover.h) ------------------
 // A pass of its own beside one expansion launch (the expansion kernels do not
 // change): `generated` over the launch's parents [lo, hi) — the lane walk of
@@ -2156,6 +2170,13 @@ static hipError_t launch_cover_t(const Params& P, const DevBufs& B, u64 lo, u64 
     return hipGetLastError();
 }
 
+template <int S, int K>
+static hipError_t launch_check_t(const Params& P, const u32* in, u64 n, int* out, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL((k_check<S, K>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, in, n, out);
+    return hipGetLastError();
+}
+
 // ---- host launchers (template dispatch on S, K, symmetry) ------------------------------
 // Blocks of the expansion kernels (RMC_EXPAND_GRID for A/B runs; default
 // 1024 = the resident blocks at 4 waves/SIMD: 4 per CU x 256 CUs, so a launch
@@ -2326,6 +2347,7 @@ static hipError_t launch_sk(bool sym, bool verify, Op op, const Params& P, const
                                             hipStream_t st);                                                    \
     hipError_t launch_cover_shape_##SS##_##KK(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo,       \
                                               u64 nhi, u64 n_init, unsigned long long* cov, hipStream_t st);    \
+    hipError_t launch_check_shape_##SS##_##KK(const Params& P, const u32* in, u64 n, int* out, hipStream_t st); \
     hipError_t set_fp_salt_shape_##SS##_##KK(u64 salt, u64 ep, hipStream_t st);
 RMC_SHAPES(RMC_SHAPE_DECLS)
 
@@ -2344,6 +2366,9 @@ RMC_SHAPES(RMC_SHAPE_DECLS)
     hipError_t launch_cover_shape_##SS##_##KK(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo,       \
                                               u64 nhi, u64 n_init, unsigned long long* cov, hipStream_t st) {   \
         return launch_cover_t<SS, KK>(P, B, lo, hi, nlo, nhi, n_init, cov, st);                                \
+    }                                                                                                           \
+    hipError_t launch_check_shape_##SS##_##KK(const Params& P, const u32* in, u64 n, int* out, hipStream_t st) { \
+        return launch_check_t<SS, KK>(P, in, n, out, st);                                                       \
     }                                                                                                           \
     hipError_t set_fp_salt_shape_##SS##_##KK(u64 salt, u64 ep, hipStream_t st) {                                \
         /* staged on this call's stack and waited for: concurrent callers (one host */                          \
@@ -2403,6 +2428,14 @@ hipError_t launch_cover(const Shape& sh, const Params& P, const DevBufs& B, u64 
     if (sh.S == SS && sh.K == KK) return launch_cover_shape_##SS##_##KK(P, B, lo, hi, nlo, nhi, n_init, cov, st);
     RMC_SHAPES(RMC_CCASE)
 #undef RMC_CCASE
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_check(const Shape& sh, const Params& P, const u32* in, u64 n, int* out, hipStream_t st) {
+#define RMC_KCASE(SS, KK) \
+    if (sh.S == SS && sh.K == KK) return launch_check_shape_##SS##_##KK(P, in, n, out, st);
+    RMC_SHAPES(RMC_KCASE)
+#undef RMC_KCASE
     return hipErrorInvalidValue;
 }
 #endif  // RMC_SHAPE_S

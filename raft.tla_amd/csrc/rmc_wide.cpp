@@ -396,6 +396,31 @@ int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_vie
     return 0;
 }
 
+// rmc_check_states on the wide layout.  RMC_WSIM (read per call) picks the check as it
+// picks the simulator's kernel: 1 (default) the wave's, 0 the thread's.
+int check_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t mask, int32_t* violated) {
+    std::vector<WState> in(n);
+    std::string why;
+    for (size_t t = 0; t < n; ++t)
+        if (encode_wide(c->WM.S, states[t], &in[t], &why))
+            return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
+    const char* e = getenv("RMC_WSIM");
+    const int wave = e ? atoi(e) : 1;
+    WModel M = c->WM;
+    M.inv_mask = (int)mask;
+    DevScratch<WState> d_in;
+    DevScratch<int> d_out;
+    HIPCHK(c, d_in.alloc(n));
+    HIPCHK(c, d_out.alloc(n));
+    HIPCHK(c, hipMemcpy(d_in.get(), in.data(), n * sizeof(WState), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_wcheck(M, d_in.get(), (u64)n, d_out.get(), wave, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    std::vector<int> v(n);
+    HIPCHK(c, hipMemcpy(v.data(), d_out.get(), n * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < n; ++t) violated[t] = v[t] ? 1 << (v[t] - 1) : 0;
+    return 0;
+}
+
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_beh, std::vector<rmc_state_view>* rec) {
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<WState> inits;

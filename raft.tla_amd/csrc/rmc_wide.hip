@@ -626,6 +626,29 @@ __global__ __launch_bounds__(64 * WSIM_WAVES) __attribute__((amdgpu_waves_per_eu
     }
 }
 
+// The invariants of n given states (rmc_check_states): one thread per state with
+// the BFS's and k_wsimulate's wcheck_invariants, or one wave per state on a copy
+// in LDS with k_wsimulate_w's w_check_invariants_wave.  They call those and
+// nothing else.
+__global__ __launch_bounds__(64) void k_wcheck(const WModel M, const WState* in, u64 n, int* out) {
+    const u64 p = (u64)blockIdx.x * 64ull + threadIdx.x;
+    if (p >= n) return;
+    out[p] = wcheck_invariants(M, in[p]);
+}
+__global__ __launch_bounds__(64 * WSIM_WAVES) void k_wcheck_w(const WModel M, const WState* in, u64 n, int* out) {
+    __shared__ WState s_buf[WSIM_WAVES];
+    const int wv = (int)(threadIdx.x >> 6), ln = (int)(threadIdx.x & 63);
+    for (u64 p = (u64)blockIdx.x * WSIM_WAVES + wv; p < n; p += (u64)gridDim.x * WSIM_WAVES) {  // wave-uniform
+        u64* x = reinterpret_cast<u64*>(&s_buf[wv]);
+        const u64* y = reinterpret_cast<const u64*>(&in[p]);
+        for (int k = ln; k < WWORDS; k += 64) x[k] = y[k];
+        w_wsync();
+        const int v = w_check_invariants_wave(M, s_buf[wv]);
+        if (ln == 0) out[p] = v;
+        w_wsync();  // every lane has read the record before the next state overwrites it
+    }
+}
+
 // ---- host launchers ---------------------------------------------------------------
 static unsigned grid_for(u64 n, u64 threads, u64 maxg) {
     const u64 b = (n + threads - 1) / threads;
@@ -738,6 +761,14 @@ hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u6
     else
         hipLaunchKernelGGL(k_wsimulate, dim3(grid_for(n_beh, 64, 16384)), dim3(64), 0, st, M, inits, n_init, n_beh,
                            depth, seed, mode, out, rec_beh, rec);
+    return hipGetLastError();
+}
+hipError_t launch_wcheck(const WModel& M, const WState* in, u64 n, int* out, int wave, hipStream_t st) {
+    if (!n) return hipSuccess;
+    if (wave)
+        hipLaunchKernelGGL(k_wcheck_w, dim3(grid_for(n, WSIM_WAVES, 8192)), dim3(64 * WSIM_WAVES), 0, st, M, in, n, out);
+    else
+        hipLaunchKernelGGL(k_wcheck, dim3(grid_for(n, 64, 1u << 20)), dim3(64), 0, st, M, in, n, out);
     return hipGetLastError();
 }
 

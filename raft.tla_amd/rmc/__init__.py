@@ -139,7 +139,8 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_config_from_files", "rmc_probe_bench", "rmc_rccl_unique_id", "rmc_shard",
            "rmc_set_seed", "rmc_simulate", "rmc_sim_replay", "rmc_set_fp_bits",
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
-           "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action")
+           "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action",
+           "rmc_check_states")
 
 _lib = None
 
@@ -211,6 +212,9 @@ def native():
         lib.rmc_get_coverage.restype = C.c_int
         lib.rmc_coverage_action.argtypes = [C.c_int32]
         lib.rmc_coverage_action.restype = C.c_char_p
+        lib.rmc_check_states.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.c_uint32,
+                                         C.POINTER(C.c_int32)]
+        lib.rmc_check_states.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -421,3 +425,12 @@ class Checker:
         n = C.c_size_t()
         self._check(self.lib.rmc_expand(self.ctx, arr, len(views), out, cap, C.byref(n)))
         return [out[k] for k in range(min(n.value, cap))]
+
+    def check_states(self, views, invariants=0):
+        """rmc_check_states: per view 0, or the RMC_INV_* bit of the first invariant of
+        the mask (0 = the ctx's own) that the device code finds violated.  `views`:
+        a sequence of StateView, or a ctypes array of them (passed as it is)."""
+        arr = views if isinstance(views, C.Array) else (StateView * len(views))(*views)
+        out = (C.c_int32 * len(views))()
+        self._check(self.lib.rmc_check_states(self.ctx, arr, len(views), invariants, out))
+        return list(out)

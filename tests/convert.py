@@ -185,6 +185,112 @@ def random_state_edge(model, rng: random.Random):
     )
 
 
+def near_invariant_state(model, rng: random.Random):
+    """A random type-correct state close to the named invariants, so that each of
+    them holds on a good share of the draws and fails on another (uniform states
+    violate the log invariants almost always at S = 5): terms from a window of
+    three, half of the time one term everywhere; every log a prefix of one master
+    log of nondecreasing terms with, now and then, one perturbed entry; small
+    commit indexes (sometimes past the log's end); votes agreeing on one server;
+    roles weighted 5:3:2; sparse vote sets; an election staged for one candidate
+    in a third of the states (a quorum of its term voting for it or not at all,
+    with or without its term in the master log: CandidateTermNotInLog); a few
+    messages, mostly derived from their sender's term and log.  Every field
+    stays within the model's bounds, so the state is packable where the model is."""
+    S, V = model.n_servers, model.n_values
+    T, L = model.max_term, model.max_log
+    lo = rng.randint(1, max(1, T - 2))
+    terms = list(range(lo, min(T, lo + 2) + 1))
+    top = terms[-1]
+    if rng.random() < 0.5:
+        ct = [rng.choice(terms)] * S
+    else:
+        ct = [rng.choice(terms) for _ in range(S)]
+    state = [rng.choices([R.FOLLOWER, R.CANDIDATE, R.LEADER], weights=[5, 3, 2])[0] for _ in range(S)]
+    fav = rng.randrange(S)
+    voted = [fav if rng.random() < 0.6 else rng.choice([R.NIL] + list(range(S))) for _ in range(S)]
+    # the master log: nondecreasing terms of the window (below its top in half of the staged elections)
+    staged = rng.random() < 0.33
+    cap = top - 1 if (staged and rng.random() < 0.5 and top > 1) else top
+    mt = sorted(rng.randint(max(1, cap - 2), cap) for _ in range(rng.choice([L, L, rng.randint(0, L)])))
+    master = tuple(R.entry(t, rng.randrange(V)) for t in mt)
+    if staged:
+        i = rng.randrange(S)
+        state[i], ct[i] = R.CANDIDATE, top
+        for j in rng.sample(range(S), rng.randint(S // 2, S)):  # around a quorum of its term
+            ct[j] = top
+            voted[j] = rng.choice([i, R.NIL])
+
+    def a_log():
+        lg = list(master[:rng.choice([len(master), len(master), rng.randint(0, len(master))])])
+        if lg and rng.random() < 0.15:
+            x = rng.randrange(len(lg))
+            lg[x] = R.entry(rng.choice(terms), rng.randrange(V))
+        return tuple(lg)
+
+    log = [a_log() for _ in range(S)]
+    commit = []
+    for i in range(S):
+        r = rng.random()
+        c = 0 if r < 0.5 else 1 if r < 0.75 else len(log[i]) + 1 if r < 0.85 else rng.randint(0, L)
+        commit.append(min(c, L))
+    sparse = lambda p: frozenset(k for k in range(S) if rng.random() < p)
+
+    def derived():  # a message as its sender would have sent it in this state
+        i, j = rng.randrange(S), rng.randrange(S)
+        t = rng.choice([R.RVQ, R.RVP, R.AEQ, R.AEP])
+        c = dict(mtype=t, mterm=ct[i] if rng.random() < 0.8 else rng.randint(0, ct[i]), msource=i, mdest=j)
+        if t == R.RVQ:
+            return R.rec(mlastLogTerm=R.last_term(log[i]), mlastLogIndex=len(log[i]), **c)
+        if t == R.RVP:
+            return R.rec(mvoteGranted=rng.random() < 0.5, mlog=log[i], **c)
+        if t == R.AEQ:
+            if log[i] and rng.random() < 0.8:
+                p = rng.randrange(len(log[i]))
+                if p and rng.random() < 0.25:  # all right but for the previous entry's term
+                    return R.rec(mprevLogIndex=p, mprevLogTerm=rng.choice([0, lo, top]), mentries=(log[i][p],),
+                                 mcommitIndex=min(commit[i], p + 1), **c)
+                return R.rec(mprevLogIndex=p, mprevLogTerm=R.rget(log[i][p - 1], "term") if p else 0,
+                             mentries=(log[i][p],), mcommitIndex=min(commit[i], p + 1), **c)
+            p = len(log[i])
+            return R.rec(mprevLogIndex=p, mprevLogTerm=R.last_term(log[i]), mentries=(),
+                         mcommitIndex=min(commit[i], p), **c)
+        return R.rec(msuccess=rng.random() < 0.5, mmatchIndex=rng.randint(0, L), **c)
+
+    def wild():
+        ent = lambda: R.entry(rng.choice(terms), rng.randrange(V))
+        t = rng.choice([R.RVQ, R.RVP, R.AEQ, R.AEP])
+        c = dict(mtype=t, mterm=rng.randint(0, T), msource=rng.randrange(S), mdest=rng.randrange(S))
+        if t == R.RVQ:
+            return R.rec(mlastLogTerm=rng.randint(0, T), mlastLogIndex=rng.randint(0, L), **c)
+        if t == R.RVP:
+            return R.rec(mvoteGranted=rng.random() < 0.5, mlog=tuple(ent() for _ in range(rng.randint(0, L))), **c)
+        if t == R.AEQ:
+            return R.rec(mprevLogIndex=rng.randint(-1, L), mprevLogTerm=rng.randint(0, T),
+                         mentries=tuple(ent() for _ in range(rng.randint(0, 1))),
+                         mcommitIndex=rng.randint(0, L), **c)
+        return R.rec(msuccess=rng.random() < 0.5, mmatchIndex=rng.randint(0, L), **c)
+
+    n_msgs = rng.randint(0, min(3, model.max_msgs)) if rng.random() < 0.9 else rng.randint(0, model.max_msgs)
+    all_derived = rng.random() < 0.5
+    msgs = {}
+    for _ in range(n_msgs):
+        m = derived() if (all_derived or rng.random() < 0.6) else wild()
+        msgs[m] = rng.choice([1, 1, rng.randint(1, model.max_dup)])
+    return R.State(
+        messages=frozenset(msgs.items()),
+        currentTerm=tuple(ct),
+        state=tuple(state),
+        votedFor=tuple(voted),
+        log=tuple(log),
+        commitIndex=tuple(commit),
+        votesResponded=tuple(sparse(0.3) for _ in range(S)),
+        votesGranted=tuple(sparse(0.15) for _ in range(S)),
+        nextIndex=tuple(tuple(rng.randint(1, L + 1) for _ in range(S)) for _ in range(S)),
+        matchIndex=tuple(tuple(rng.randint(0, L) for _ in range(S)) for _ in range(S)),
+    )
+
+
 def check_trace(model, trace, violated_inv, violation_depth):
     """A counterexample [(family, lane, StateView)] must be a behaviour of the
     spec (Python restatement) from Init to a state violating `violated_inv`,

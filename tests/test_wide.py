@@ -63,7 +63,8 @@ def test_wide_layout_matches_oracle_levels(name, force_wide, wide_record):
                                                                   g["left_on_queue"])
 
 
-@pytest.mark.parametrize("name", ["bug_one_leader", "bug_log_matching", "messages_small"])
+@pytest.mark.parametrize("name", ["bug_one_leader", "bug_log_matching", "messages_small", "bug_leader_votes",
+                                  "bug_quorum_log", "bug_leader_complete"])
 def test_wide_layout_violation_and_trace(name, force_wide, wide_record):
     g = GOLDEN[name]
     p = g["params"]

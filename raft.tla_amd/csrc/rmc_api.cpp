@@ -53,6 +53,7 @@ void fill_params(rmc_ctx* c) {
     c->sh.K = kcap_for(g.max_msgs);
     c->sh.sym = (g.flags & RMC_FLAG_SYMMETRY) != 0;
     c->sh.verify = (g.flags & RMC_FLAG_VERIFY_STATES) != 0;
+    c->k = shape_kernels(c->sh.S, c->sh.K);
     c->NW = 2 * c->sh.S + c->sh.K;
     Params& P = c->P;
     P.V = g.n_values;
@@ -126,7 +127,7 @@ int begin_set(rmc_ctx* c, bool tagged) {
     if (e.clear) HIPCHK(c, launch_fill(c->B.table, c->table_slots * 8, 0, c->st));
     c->set_epoch = e.epoch;
     if (c->sh.verify) HIPCHK(c, launch_fill(c->B.sidx, c->table_slots * 8, 0xFF, c->st));
-    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+    HIPCHK(c, set_fp_salt(*c->k, c->cfg.seed, c->set_epoch, c->st));
     return 0;
 }
 
@@ -137,7 +138,7 @@ int seed_init(rmc_ctx* c) {
     std::string why;
     if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, launch(c, Op::Seed, 1, 0, c->d_staged));
+    HIPCHK(c, c->k->seed(c->sh.sym, c->P, c->PT, c->B, c->d_staged, 1, c->st));
     return 0;
 }
 
@@ -273,6 +274,7 @@ int rmc_create(const rmc_config* cfg, rmc_ctx** out) {
         rmc_destroy(c);
         return rc;
     };
+    if (!c->k) { c->err = "no kernels built for this shape"; return bail(RMC_E_INVAL); }
     if (hipSetDevice(cfg->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(RMC_E_NOGPU); }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) { c->err = "hipGetDeviceProperties failed"; return bail(RMC_E_NOGPU); }
@@ -439,9 +441,9 @@ static int start_run(rmc_ctx* c, int* depth) {
     if (int rc = seed_init(c)) return rc;
     if (int rc = read_counters(c)) return rc;
     *depth = seed_done(c);
-    if (c->sh.verify) HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
+    if (c->sh.verify) HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, 0, c->h_ctr->count, c->st));
     if (cover_on(c))  // row Init: the one initial state generated, and what the seed stored
-        HIPCHK(c, launch_cover(c->sh, c->P, c->B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
+        HIPCHK(c, c->k->cover(c->P, c->B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
     return 0;
 }
 
@@ -460,7 +462,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     if (resume) {
         c->res.left_on_queue = 0;
         c->res.seconds = 0;
-        HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+        HIPCHK(c, set_fp_salt(*c->k, c->cfg.seed, c->set_epoch, c->st));
         c->h_ctr->count = c->level_start.back();
         if (int rc = reset_counters(c, true)) return rc;
         depth = c->resume_depth;
@@ -535,18 +537,18 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
             }
             // coverage reads Counters.count back after every launch, so it is current here
             const u64 cov_before = c->h_ctr->count;
-            HIPCHK(c, launch(c, Op::Expand, a, b));
+            HIPCHK(c, c->k->expand(c->sh.sym, c->sh.verify, c->P, c->PT, c->B, a, b, c->st));
             c->res.expand_launches += 1;
             if (c->sh.sym && !c->sh.verify) {
-                HIPCHK(c, launch(c, Op::Ties));
+                HIPCHK(c, c->k->ties(c->P, c->PT, c->B, c->st));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
             }
             if (c->sh.verify) {
                 const u64 before = c->h_ctr->count;
                 if (int rc = read_counters(c)) return rc;
                 if (c->h_ctr->overflow) break;
-                HIPCHK(c, launch(c, Op::Publish, before, c->h_ctr->count));
-                HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
+                HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, before, c->h_ctr->count, c->st));
+                HIPCHK(c, c->k->verify(c->sh.sym, c->P, c->PT, c->B, c->h_ctr->vcount, c->st));
                 HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
                 c->h_ctr->vcount = 0;
                 if (c->h_ctr->hcount)  // hits on spilled owners: against their host copies
@@ -574,7 +576,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     if (int rc = read_counters(c)) return rc;
                     if (c->h_ctr->overflow || c->h_ctr->table_full) break;
                 }
-                HIPCHK(c, launch_cover(c->sh, c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+                HIPCHK(c, c->k->cover(c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
             }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
@@ -667,7 +669,7 @@ int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* in
             unsigned long long n = 0;
             if (hipMemcpy(d_in.get(), cur.data(), NW * 4, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemset(d_cnt.get(), 0, 8) != hipSuccess ||
-                launch(c, Op::List, 1, 0, d_in.get(), d_out.get(), lanes, d_cnt.get()) != hipSuccess ||
+                c->k->list(c->sh.sym, c->P, c->PT, d_in.get(), 1, d_out.get(), lanes, d_cnt.get(), c->st) != hipSuccess ||
                 hipStreamSynchronize(c->st) != hipSuccess ||
                 hipMemcpy(&n, d_cnt.get(), 8, hipMemcpyDeviceToHost) != hipSuccess ||
                 hipMemcpy(recs.data(), d_out.get(), std::min<u64>(n, lanes) * RW * 4, hipMemcpyDeviceToHost) != hipSuccess)
@@ -729,7 +731,7 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
     SimCounters h;
     float ms = 0.f;
     if (int rc = sim_timed(c, d_out.get(), &h, &ms, [&] {
-            return launch_sim(c->sh, P, d_init.get(), n_init, sc->behaviours, sc->depth, sc->seed, sc->mode, d_out.get(),
+            return c->k->simulate(P, d_init.get(), n_init, sc->behaviours, sc->depth, sc->seed, sc->mode, d_out.get(),
                               rec_beh, d_rec.get(), c->st);
         }))
         return rc;
@@ -836,7 +838,7 @@ int rmc_expand(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view
     HIPCHK(c, d_cnt.alloc(1));
     HIPCHK(c, hipMemcpy(d_in.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(d_cnt.get(), 0, 8));
-    HIPCHK(c, launch(c, Op::List, (u64)n, 0, d_in.get(), d_out.get(), rcap, d_cnt.get()));
+    HIPCHK(c, c->k->list(c->sh.sym, c->P, c->PT, d_in.get(), (u64)n, d_out.get(), rcap, d_cnt.get(), c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     unsigned long long cnt = 0;
     HIPCHK(c, hipMemcpy(&cnt, d_cnt.get(), 8, hipMemcpyDeviceToHost));
@@ -888,7 +890,7 @@ int rmc_check_states(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_
     HIPCHK(c, d_in.alloc(packed.size()));
     HIPCHK(c, d_out.alloc(n));
     HIPCHK(c, hipMemcpy(d_in.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, launch_check(c->sh, P, d_in.get(), (u64)n, d_out.get(), c->st));
+    HIPCHK(c, c->k->check(P, d_in.get(), (u64)n, d_out.get(), c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     std::vector<int> v(n);
     HIPCHK(c, hipMemcpy(v.data(), d_out.get(), n * sizeof(int), hipMemcpyDeviceToHost));

@@ -203,7 +203,7 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     // a dumped set keeps its entries' epoch tag (header pad_); states rehashed
     // below go into an untagged set
     c->set_epoch = h.slots ? std::min<u32>(h.pad_, 255u) : 0u;
-    HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+    HIPCHK(c, set_fp_salt(*c->k, c->cfg.seed, c->set_epoch, c->st));
     if (int r2 = reset_counters(c, false)) return r2;
     const u64 ls0 = c->spill.dev_links ? 0 : s;  // links below ls0 go to the host
     if (ls0) get(c->spill.h_parent, ls0 * 8);
@@ -221,7 +221,7 @@ int rmc_recover(rmc_ctx* c, const char* path) {
             DevBufs T = c->B;
             T.store = (u32*)((uintptr_t)area - (uintptr_t)(p * W));
             T.wmask = ~0ull;  // indexed through the biased pointer, not the ring
-            if (!rc) HIPCHK(c, launch_on(c, T, c->st, Op::Rehash, p, p + k));
+            if (!rc) HIPCHK(c, c->k->rehash(c->sh.sym, c->P, c->PT, T, p, p + k, c->st));
             if (!rc) HIPCHK(c, hipStreamSynchronize(c->st));
         }
     }
@@ -239,8 +239,8 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     fclose(f);
     if (rc) return rc;
     if (s) spill_rebase(c, s);
-    if (!h.slots) HIPCHK(c, launch(c, Op::Rehash, s, h.count));
-    if (c->sh.verify) HIPCHK(c, launch(c, Op::Publish, 0, h.count));
+    if (!h.slots) HIPCHK(c, c->k->rehash(c->sh.sym, c->P, c->PT, c->B, s, h.count, c->st));
+    if (c->sh.verify) HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, 0, h.count, c->st));
     if (int r2 = read_counters(c)) return r2;
     if (c->h_ctr->table_full) return fail(c, RMC_E_CAPACITY, "recover: fingerprint set full");
     if (c->h_ctr->overflow) return fail(c, RMC_E_IO, "recover: the checkpoint holds duplicate states");

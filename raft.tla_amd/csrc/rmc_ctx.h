@@ -127,6 +127,7 @@ struct SpillState {
 struct rmc_ctx {
     rmc_config cfg{};
     rmc::Shape sh{};
+    const rmc::ShapeKernels* k = nullptr;  // the launchers of shape (sh.S, sh.K), resolved at create
     rmc::Params P{};
     rmc::PermTable PT{};
     int NW = 0;  // 32-bit words per packed state
@@ -260,18 +261,6 @@ int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, rmc::i64
 void fill_wide_model(rmc_ctx* c);
 inline SmokeShape smoke_shape(const rmc_config& g, bool wide) {  // what SmokeInit draws for (rmc_codec.h)
     return {g.n_servers, g.n_values, wide, wide ? rmc::wide::KW : kcap_for(g.max_msgs)};
-}
-
-// A kernel of this ctx's shape and model (rmc_internal.h launch): on c->B and the
-// ctx stream, or on other buffers / another stream.
-inline hipError_t launch_on(rmc_ctx* c, const rmc::DevBufs& B, hipStream_t st, rmc::Op op, rmc::u64 a = 0,
-                            rmc::u64 b = 0, const rmc::u32* in = nullptr, rmc::u32* out = nullptr, rmc::u64 cap = 0,
-                            unsigned long long* count = nullptr) {
-    return rmc::launch(c->sh, op, c->P, c->PT, B, a, b, in, out, cap, count, st);
-}
-inline hipError_t launch(rmc_ctx* c, rmc::Op op, rmc::u64 a = 0, rmc::u64 b = 0, const rmc::u32* in = nullptr,
-                         rmc::u32* out = nullptr, rmc::u64 cap = 0, unsigned long long* count = nullptr) {
-    return launch_on(c, c->B, c->st, op, a, b, in, out, cap, count);
 }
 
 // A per-call allocation of n T's (hipMalloc; Pinned: hipHostMalloc), freed at scope exit.

@@ -144,7 +144,7 @@ int start(rmc_ctx* c, Run& R) {
     if (!resume) {
         if (int rc = begin_set(c, !verify && !c->sh.sym)) return rc;
     } else {
-        HIPCHK(c, set_fp_salt(c->sh, c->cfg.seed, c->set_epoch, c->st));
+        HIPCHK(c, set_fp_salt(*c->k, c->cfg.seed, c->set_epoch, c->st));
         c->h_ctr->count = c->level_start.back();
     }
     if (int rc = reset_counters(c, resume)) return rc;
@@ -157,7 +157,7 @@ int start(rmc_ctx* c, Run& R) {
         c->level_start.push_back(c->h_ctr->count);
     }
     if (verify && !resume && c->h_ctr->count)  // slot -> store index of the initial state(s)
-        HIPCHK(c, launch(c, Op::Publish, 0, c->h_ctr->count));
+        HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, 0, c->h_ctr->count, c->st));
     R.count_before.resize((size_t)W);
     for (int r = 0; r < W; ++r) {
         R.total_prev += R.rows[(size_t)r].count;
@@ -190,7 +190,7 @@ int replicated_level(rmc_ctx* c, Run& R, u64 lo, u64 hi, u64 ftot) {
     DistState& D = c->dist;
     const u64 RBR = (u64)(c->NW + 6) * 4;  // the level's record (RepRec)
     D.phase = "replicated level (frontier all-gather)";
-    if (hi > lo) HIPCHK(c, launch(c, Op::PackRep, lo, hi, nullptr, D.rep_send));
+    if (hi > lo) HIPCHK(c, c->k->pack_rep(c->B, lo, hi, D.rep_send, c->st));
     HIPCHK(c, hipEventRecord(D.ev_c, c->st));
     HIPCHK(c, hipStreamWaitEvent(D.xs, D.ev_c, 0));
     if (int rc = gather_level(c, R.fsz, RBR)) return rc;
@@ -201,7 +201,7 @@ int replicated_level(rmc_ctx* c, Run& R, u64 lo, u64 hi, u64 ftot) {
     Bb.rep = D.rep_buf;
     // one launch (rep_max <= 2^24 records); timed by events read after the level end
     HIPCHK(c, hipEventRecord(D.set[0].k0, c->st));
-    HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandRep, 0, ftot));
+    HIPCHK(c, c->k->expand_rep(c->P, c->PT, Bb, 0, ftot, c->st));
     HIPCHK(c, hipEventRecord(D.set[0].k1, c->st));
     R.rep_timed = ftot != 0;
     c->res.expand_launches += 1;
@@ -231,10 +231,10 @@ int enqueue_round(rmc_ctx* c, Run& R, u64 k) {
     } else if (R.cursor < R.hi) {
         const u64 n = round_states(R.hi - R.cursor, c->B.kcap, D.fill, R.rho, R.split_cap, 1ull << kMaxLaunchLog2);
         HIPCHK(c, hipEventRecord(S.k0, c->st));
-        HIPCHK(c, launch_on(c, Bb, c->st, Op::ExpandDist, R.cursor, R.cursor + n));
+        HIPCHK(c, c->k->expand_dist(c->sh.sym, c->sh.verify, c->P, c->PT, Bb, R.cursor, R.cursor + n, c->st));
         // the pool flush's remote successors: keyed and routed to the outboxes
         if (W > 1 && !verify && !c->sh.sym)
-            HIPCHK(c, launch_on(c, Bb, c->st, Op::Route));
+            HIPCHK(c, c->k->route(c->P, Bb, c->st));
         HIPCHK(c, hipEventRecord(S.k1, c->st));
         S.timed = 1;
         c->res.expand_launches += 1;
@@ -246,10 +246,10 @@ int enqueue_round(rmc_ctx* c, Run& R, u64 k) {
         if (int rc = read_counters(c)) return rc;
         const u64 c1 = c->h_ctr->count;
         if (c1 > R.vpub)
-            HIPCHK(c, launch(c, Op::Publish, R.vpub, c1));
+            HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, R.vpub, c1, c->st));
         R.vpub = c1;
         if (c->h_ctr->vcount) {
-            HIPCHK(c, launch(c, Op::Verify, c->h_ctr->vcount));
+            HIPCHK(c, c->k->verify(c->sh.sym, c->P, c->PT, c->B, c->h_ctr->vcount, c->st));
             HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
         }
     }
@@ -309,9 +309,7 @@ int phase1(rmc_ctx* c, DistState::Set& S, const RoundPlan& rp) {
     D.phase = "phase 1 (replies)";
     const PeerBlocks& Y = rp.replies;
     if (int rc = a2a(c, D.rep_out, Y.soff, Y.scnt, D.rep_in, Y.roff, Y.rcnt)) return rc;
-    if (rp.mx)
-        HIPCHK(c, launch_on(c, set_bufs(c, S), D.xs, Op::MaterializeRemote, rp.mx, 0,
-                            reinterpret_cast<const u32*>(D.rep_in)));
+    if (rp.mx) HIPCHK(c, c->k->materialize_remote(c->P, set_bufs(c, S), D.rep_in, rp.mx, 0, D.xs));
     HIPCHK(c, hipEventRecord(S.ev_free, D.xs));  // the set's keys and tickets are consumed
     HIPCHK(c, hipMemcpyAsync(D.h_sa, D.sa, 16 * (u64)W, hipMemcpyDeviceToHost, D.xs));
     HIPCHK(c, hipEventRecord(D.ev_acc, D.xs));
@@ -331,17 +329,16 @@ int phase2(rmc_ctx* c, Run& R, const u64* cx) {
     if (tot_st > (u64)D.world * c->B.kcap) return fail(c, RMC_E_CAPACITY, "phase-2 inbox full at " + where(c));
     const PeerBlocks& T = sp.states;
     if (int rc = a2a(c, c->B.st_out, T.soff, T.scnt, D.st_in, T.roff, T.rcnt)) return rc;
-    if (tot_st)
-        HIPCHK(c, launch_on(c, c->B, D.xs, Op::StoreRemote, tot_st, 0, D.st_in));
+    if (tot_st) HIPCHK(c, c->k->store_remote(c->P, c->B, D.st_in, tot_st, D.xs));
     if (verify && tot_st) {  // publish the received new states, then compare the seen ones
         HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
         if (int rc = xwait(c, D.ev_h)) return rc;
         if (int rc = read_counters(c)) return rc;
         const u64 c2 = c->h_ctr->count;
         if (c2 > R.vpub)
-            HIPCHK(c, launch_on(c, c->B, D.xs, Op::Publish, R.vpub, c2));
+            HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, R.vpub, c2, D.xs));
         R.vpub = c2;
-        HIPCHK(c, launch_on(c, c->B, D.xs, Op::CompareRemote, tot_st, 0, D.st_in));
+        HIPCHK(c, c->k->compare_remote(c->sh.sym, c->P, c->PT, c->B, D.st_in, tot_st, D.xs));
         HIPCHK(c, hipEventRecord(D.ev_h, D.xs));
         if (int rc = xwait(c, D.ev_h)) return rc;
     }

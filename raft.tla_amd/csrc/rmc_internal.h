@@ -101,47 +101,53 @@ struct Shape {
     bool verify;  // full-state verification (single GPU)
 };
 
-// The kernels of one shape, by what they do with launch()'s arguments.
-enum class Op {
-    Expand,             // the single-GPU expansion over store[a, b)
-    Seed,               // k_seed of `a` staged states `in`
-    List,               // k_list of `a` states `in` into `out` (cap records, *count)
-    ExpandDist,         // the sharded expansion over store[a, b) (outbox / pool in B)
-    Publish,            // k_publish over store[a, b) (verification: slot -> store index)
-    Verify,             // k_verify of `a` deferred hits in B.vbuf
-    Rehash,             // k_rehash of the stored states [a, b) (recovery)
-    MaterializeRemote,  // k_materialize_remote of window [b, b + a) of each destination's keys, in = replies
-    StoreRemote,        // k_store_remote of `a` received state records `in`
-    Ties,               // k_ties over the deferred tied successors (count on the device)
-    CompareRemote,      // k_compare_remote of `a` received state records `in` (sharded verification)
-    ExpandRep,          // k_expand_dist<REP> over the replicated level's records B.rep[a, b)
-    PackRep,            // k_pack_rep of this rank's stored states [a, b) into records at `out`
-    Route,              // k_route: key the pool's records and fill the outboxes (counts on the device)
-    VerifyHost,         // k_verify_host of `a` hits B.hbuf[b, b + a) against their owners' host copies
-                        // staged at `in` (verification + spill)
-};
-hipError_t launch(const Shape& sh, Op op, const Params& P, const PermTable& PT, const DevBufs& B, u64 a, u64 b,
-                  const u32* in, u32* out, u64 cap, unsigned long long* count, hipStream_t st);
-
 // Simulation counters (k_simulate).
 typedef int64_t i64;
 struct SimCounters {
     u64 steps, truncated, deadlocked;
     u64 viol;  // min over violations of (depth << 44 | invariant << 40 | behaviour), ~0 = none
 };
-hipError_t launch_sim(const Shape& sh, const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, u64 seed,
-                      int mode, SimCounters* out, i64 rec_beh, u32* rec, hipStream_t st);
 
-// rmc_check_states: out[t] = check_invariants (0, or 1 + the bit index of the first violated
-// invariant of P.inv_mask) of caller state t of `in` (n packed states of the shape).
-hipError_t launch_check(const Shape& sh, const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
-
-// Action coverage (RMC_FLAG_COVERAGE): the pass beside one expansion launch over
-// the parents [lo, hi) — their enabled lanes into cov[0 .. COV_ROWS) by action
-// (rmc_cover.h) — and the states it added, [nlo, nhi), into cov[COV_ROWS .. 2 COV_ROWS)
-// by the action of their producing lane; n_init is added to row Init's generated.
-hipError_t launch_cover(const Shape& sh, const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi,
-                        u64 n_init, unsigned long long* cov, hipStream_t st);
+// The launchers of one packed shape (S servers, K bag slots), on buffers B and stream st, each
+// named after its kernel.  sym / verify are Shape's; expand_rep and route (the plain search only)
+// and ties (SYMMETRY only) go by P.symmetry, which fill_params sets from Shape.  A launch over no
+// work items launches nothing and succeeds.
+struct ShapeKernels {
+    using Expand = hipError_t(bool sym, bool verify, const Params& P, const PermTable& PT, const DevBufs& B, u64 lo,
+                              u64 hi, hipStream_t st);
+    using Range = hipError_t(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi,
+                             hipStream_t st);
+    Expand *expand, *expand_dist;  // over store[lo, hi): single GPU / sharded (outbox and pool in B)
+    hipError_t (*expand_rep)(const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi, hipStream_t st);
+    hipError_t (*route)(const Params& P, const DevBufs& B, hipStream_t st);  // k_route_fix, then k_route
+    hipError_t (*ties)(const Params& P, const PermTable& PT, const DevBufs& B, hipStream_t st);
+    hipError_t (*seed)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, const u32* staged, u64 n,
+                       hipStream_t st);
+    hipError_t (*list)(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u32* out, u64 cap,
+                       unsigned long long* count, hipStream_t st);
+    Range *publish, *rehash;  // over store[lo, hi)
+    hipError_t (*verify)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, u64 n_hits, hipStream_t st);
+    hipError_t (*verify_host)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B,
+                              const u32* staged_owners, u64 n_hits, u64 hbuf_off, hipStream_t st);
+    hipError_t (*materialize_remote)(const Params& P, const DevBufs& B, const uint8_t* reply, u64 keys_per_dest,
+                                     u64 window_off, hipStream_t st);
+    hipError_t (*store_remote)(const Params& P, const DevBufs& B, const u32* recs, u64 n, hipStream_t st);
+    hipError_t (*compare_remote)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, const u32* recs,
+                                 u64 n, hipStream_t st);
+    hipError_t (*pack_rep)(const DevBufs& B, u64 lo, u64 hi, u32* out, hipStream_t st);
+    hipError_t (*simulate)(const Params& P, const u32* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,
+                           SimCounters* out, i64 rec_beh, u32* rec, hipStream_t st);
+    // parents [lo, hi) and the states their launch added, [nlo, nhi), into cov (k_cover, rmc_dev_tools.h)
+    hipError_t (*cover)(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
+                        unsigned long long* cov, hipStream_t st);
+    hipError_t (*check)(const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
+    hipError_t (*set_salt)(u64 salt, u64 epoch, hipStream_t st);  // epoch << 56; returns after the copies
+};
+// The table of shape (S, K), defined by its object (rmc_kernels_shape.hip), and its lookup:
+// nullptr for a shape that is not built.  The tables are filled when the library loads: not
+// for use from another object's static initialiser.
+#define RMC_SHAPE_TABLE(SS, KK) kShapeKernels_##SS##_##KK
+const ShapeKernels* shape_kernels(int S, int K);
 
 // Sharded mode, phase 1 owner side: insert n received keys (12-B {k lo, k hi, s32}
 // records), reply[t] = new;
@@ -169,6 +175,8 @@ constexpr int kMaxLaunchLog2 = 25;
 // Presorted windows: k_window_order over the launch [lo, hi) for an expansion
 // grid of `grid` blocks and windows of at most wt_max tiles (B.word).
 hipError_t launch_window_order(const DevBufs& B, u64 lo, u64 hi, u64 grid, u64 wt_max, hipStream_t st);
+// One round of resident blocks of kernel k (256 threads) on this device (rmc_kernels_common.hip).
+u64 resident_grid(const void* k);
 // The slot of state index i in the store / foot / cls arrays (DevBufs.wmask).
 __host__ __device__ __forceinline__ u64 wslot(const DevBufs& B, u64 i) { return i & B.wmask; }
 // Sharded mode: move parked keys ovf[a, a + n) into the (emptied) outbox; n <= kcap.
@@ -177,11 +185,11 @@ hipError_t launch_drain(const DevBufs& B, u64 a, u64 n, hipStream_t st);
 // its lane sits at bits 56-63).
 constexpr u64 POOL_TICK = 1ull << 48;
 
-// Fingerprint salt for the kernels of shape sh on this device (0 = default
+// Fingerprint salt for the kernels of shape k on this device (0 = default
 // hash); returns after the copy (the staging value lives on the caller's stack).
 // the fingerprint salt of rmc_config.seed and the set epoch of the run (raft_packed.h
 // c_set_ep: 0 = an untagged set, cleared before the run)
-hipError_t set_fp_salt(const Shape& sh, u64 seed, u32 set_epoch, hipStream_t st);
+hipError_t set_fp_salt(const ShapeKernels& k, u64 seed, u32 set_epoch, hipStream_t st);
 
 // Sets bytes [p, p + bytes) to `byte` (the fingerprint set's clear; RMC_FILL=0: hipMemsetAsync).
 hipError_t launch_fill(void* p, u64 bytes, uint8_t byte, hipStream_t st);
@@ -229,7 +237,7 @@ struct WSucc {
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st);  // staged: B's work record (ring) / store record
 hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hipStream_t st);
 hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t st);  // the n deferred hits in B.vbuf
-// launch_cover on the wide records (k_wcover)
+// ShapeKernels::cover on the wide records (k_wcover)
 hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
                          unsigned long long* cov, hipStream_t st);
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,

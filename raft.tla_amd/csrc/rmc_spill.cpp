@@ -221,7 +221,7 @@ int verify_host_hits(rmc_ctx* c, u64 n) {
             memcpy(X.h_ostage + q * NW, X.h_state + ix * NW, NW * 4);
         }
         HIPCHK(c, hipMemcpyAsync(X.d_ostage, X.h_ostage, m * NW * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(c, launch(c, Op::VerifyHost, m, off, X.d_ostage));
+        HIPCHK(c, c->k->verify_host(c->sh.sym, c->P, c->PT, c->B, X.d_ostage, m, off, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));  // the pinned stage is refilled next
     }
     HIPCHK(c, hipMemsetAsync(&c->B.ctr->hcount, 0, 8, c->st));

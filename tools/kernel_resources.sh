@@ -1,6 +1,8 @@
 #!/bin/bash
 # Per-kernel VGPR / SGPR / scratch / LDS of one gfx950 object (librmc build):
 #   tools/kernel_resources.sh raft.tla_amd/_obj/rmc_kernels_3_4.o [name-regex]
+# (rmc_kernels_<S>_<K>.o: csrc/rmc_kernels_shape.hip built for one shape; rmc_kernels.o:
+# csrc/rmc_kernels_common.hip; rmc_wide.o: csrc/rmc_wide.hip)
 set -e
 obj=$1; pat=${2:-.}
 d=$(mktemp -d)

@@ -24,9 +24,9 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 10 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 11 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
-                              rmc_coverage_action (round 8); 10: rmc_check_states */
+                              rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -381,6 +381,15 @@ int rmc_expand(rmc_ctx* ctx, const rmc_state_view* states, size_t n, rmc_succ_vi
  * one-thread-per-state check the BFS uses. */
 int rmc_check_states(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint32_t invariants,
                      int32_t* violated);
+/* Test hook: keys[t] = the 64-bit key (Fp.k) the search would insert for state t:
+ * state_fp, under RMC_FLAG_SYMMETRY canon_state — the same device function k_seed,
+ * k_rehash and k_publish call.  ref != NULL: same[t] = 1 iff verification's
+ * comparison (same_state; under SYMMETRY same_orbit) finds state t equal to the
+ * stored form of state ref[t] (ref[t] < n).  Packed layout only (the wide layout
+ * has no SYMMETRY): RMC_E_INVAL on a wide ctx, for a view the encoder refuses, a
+ * NULL array with n > 0, or ref[t] >= n; n = 0 launches nothing. */
+int rmc_state_keys(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint64_t* keys,
+                   const uint32_t* ref, uint8_t* same);
 
 /* ---- simulation (TLC -simulate; Smokeraft.cfg, config 4) ---------------------
  * Replaces TLC's Simulator: random behaviours, each from a random initial state

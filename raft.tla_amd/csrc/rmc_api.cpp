@@ -898,4 +898,39 @@ int rmc_check_states(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_
     return 0;
 }
 
+int rmc_state_keys(rmc_ctx* c, const rmc_state_view* states, size_t n, uint64_t* keys, const uint32_t* ref,
+                   uint8_t* same) {
+    if (!c) return RMC_E_INVAL;
+    if (c->wide) return fail(c, RMC_E_INVAL, "rmc_state_keys: the packed layout only");
+    if (n && (!states || !keys || (ref && !same)))
+        return fail(c, RMC_E_INVAL, "rmc_state_keys: states, keys or same is NULL");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n == 0) return 0;
+    for (size_t t = 0; ref && t < n; ++t)
+        if (ref[t] >= n) return fail(c, RMC_E_INVAL, "rmc_state_keys: ref[" + std::to_string(t) + "] is not below n");
+    const int NW = c->NW;
+    std::vector<u32> packed(n * (size_t)NW);
+    std::string why;
+    for (size_t t = 0; t < n; ++t)
+        if (encode_view(c->sh.S, c->sh.K, states[t], packed.data() + t * NW, &why))
+            return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
+    DevScratch<u32> d_in, d_ref;
+    DevScratch<u64> d_keys;
+    DevScratch<unsigned char> d_same;
+    HIPCHK(c, d_in.alloc(packed.size()));
+    HIPCHK(c, d_keys.alloc(n));
+    HIPCHK(c, hipMemcpy(d_in.get(), packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    if (ref) {
+        HIPCHK(c, d_ref.alloc(n));
+        HIPCHK(c, d_same.alloc(n));
+        HIPCHK(c, hipMemcpy(d_ref.get(), ref, n * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, c->k->keys(c->sh.sym, c->P, c->PT, d_in.get(), (u64)n, d_keys.get(), ref ? d_ref.get() : nullptr,
+                         ref ? d_same.get() : nullptr, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(keys, d_keys.get(), n * 8, hipMemcpyDeviceToHost));
+    if (ref) HIPCHK(c, hipMemcpy(same, d_same.get(), n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

@@ -9,7 +9,7 @@
 //             parents and the producing lanes of its new states per action.
 //
 // and k_rehash (recovery), k_pack_rep (replicated levels), k_check (rmc_check_states),
-// k_simulate (TLC -simulate).
+// k_keys (rmc_state_keys), k_simulate (TLC -simulate).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -150,6 +150,29 @@ __global__ __launch_bounds__(256) void k_check(const Params P, const u32* in, u6
     u32 m[K];
     load_state<S, K>(in + t * (u64)NW, w, m);
     out[t] = check_invariants<S, K, true>(w, m, P);
+}
+
+// The keys of n given states, one thread per state (rmc_state_keys): the key k_seed,
+// k_rehash and k_publish compute for a stored state (state_fp, under SYMMETRY
+// canon_state; fp_weaken as there), and with ref the comparison of verification
+// (same_state, under SYMMETRY same_orbit) of state t against the record of state
+// ref[t] of the same array.  No set and no store is touched.
+template <int S, int K, bool SYM>
+__global__ __launch_bounds__(256) void k_keys(const PermTable PT, u64 fp_mask, const u32* in, u64 n, u64* keys,
+                                              const u32* ref, unsigned char* same) {
+    constexpr int NW = 2 * S + K;
+    const u64 t = (u64)blockIdx.x * 256ull + threadIdx.x;
+    if (t >= n) return;
+    PackedState<S, K> s;
+    load_state<S, K>(in + t * (u64)NW, s.w, s.m);
+    keys[t] = fp_weaken(SYM ? canon_state<S, K>(s.w, s.m, PT.code, PT.np) : state_fp<S, K>(s.w, s.m), fp_mask).k;
+    if (ref) {
+        const u32* st = in + (u64)ref[t] * (u64)NW;  // ref[t] < n: checked by the caller
+        bool eq;
+        if constexpr (SYM) eq = same_orbit<S, K>(s, st, PT);
+        else eq = same_state<S, K>(s.w, s.m, st);
+        same[t] = eq ? 1 : 0;
+    }
 }
 
 // ---- action coverage (RMC_FLAG_COVERAGE, TLC -coverage; rmc_cover.h) ------------------

@@ -141,6 +141,10 @@ struct ShapeKernels {
     hipError_t (*cover)(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
                         unsigned long long* cov, hipStream_t st);
     hipError_t (*check)(const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
+    // keys[t] = the key of in[t] (P.fp_mask applied); ref != nullptr: same[t] = in[t] compares equal to
+    // the record in[ref[t]] (k_keys, rmc_dev_tools.h)
+    hipError_t (*keys)(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u64* keys,
+                       const u32* ref, unsigned char* same, hipStream_t st);
     hipError_t (*set_salt)(u64 salt, u64 epoch, hipStream_t st);  // epoch << 56; returns after the copies
 };
 // The table of shape (S, K), defined by its object (rmc_kernels_shape.hip), and its lookup:

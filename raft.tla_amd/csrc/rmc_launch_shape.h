@@ -39,6 +39,16 @@ static hipError_t launch_check_t(const Params& P, const u32* in, u64 n, int* out
     return hipGetLastError();
 }
 
+template <int S, int K>
+static hipError_t launch_keys_t(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u64* keys,
+                                const u32* ref, unsigned char* same, hipStream_t st) {
+    if (!n) return hipSuccess;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (sym) hipLaunchKernelGGL((k_keys<S, K, true>), grid, dim3(256), 0, st, PT, P.fp_mask, in, n, keys, ref, same);
+    else hipLaunchKernelGGL((k_keys<S, K, false>), grid, dim3(256), 0, st, PT, P.fp_mask, in, n, keys, ref, same);
+    return hipGetLastError();
+}
+
 // Blocks of the expansion kernels (RMC_EXPAND_GRID for A/B runs; default
 // 1024 = the resident blocks at 4 waves/SIMD: 4 per CU x 256 CUs, so a launch
 // is one block round and every window sorts more tiles; 309.7 vs 315.6 ms per
@@ -212,6 +222,7 @@ static ShapeKernels shape_table() {
     k.simulate = launch_sim_t<S, K>;
     k.cover = launch_cover_t<S, K>;
     k.check = launch_check_t<S, K>;
+    k.keys = launch_keys_t<S, K>;
     k.set_salt = set_object_salt;
     return k;
 }

@@ -140,7 +140,7 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_set_seed", "rmc_simulate", "rmc_sim_replay", "rmc_set_fp_bits",
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
            "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action",
-           "rmc_check_states")
+           "rmc_check_states", "rmc_state_keys")
 
 _lib = None
 
@@ -215,6 +215,9 @@ def native():
         lib.rmc_check_states.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.c_uint32,
                                          C.POINTER(C.c_int32)]
         lib.rmc_check_states.restype = C.c_int
+        lib.rmc_state_keys.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+        lib.rmc_state_keys.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -434,3 +437,20 @@ class Checker:
         out = (C.c_int32 * len(views))()
         self._check(self.lib.rmc_check_states(self.ctx, arr, len(views), invariants, out))
         return list(out)
+
+    def state_keys(self, views, ref=None):
+        """rmc_state_keys: per view the 64-bit key the search would insert for it
+        (under symmetry=True the canonical key of its orbit).  With ref (one index
+        into views per view): (keys, same), same[t] = 1 iff verification's
+        comparison finds view t equal to the stored form of view ref[t].  `views`:
+        a sequence of StateView, or a ctypes array of them (passed as it is)."""
+        arr = views if isinstance(views, C.Array) else (StateView * len(views))(*views)
+        keys = (C.c_uint64 * len(views))()
+        if ref is None:
+            self._check(self.lib.rmc_state_keys(self.ctx, arr, len(views), keys, None, None))
+            return list(keys)
+        assert len(ref) == len(views)
+        refs = (C.c_uint32 * len(views))(*ref)
+        same = (C.c_uint8 * len(views))()
+        self._check(self.lib.rmc_state_keys(self.ctx, arr, len(views), keys, refs, same))
+        return list(keys), list(same)

@@ -58,6 +58,10 @@ CONFIGS = {
     "s4_sym_prefix16": (4, 1, 2, 1, 2, 1, 0, 1, 1, 16),
     "s5_sym_prefix16": (5, 2, 2, 1, 2, 1, 0, 1, 1, 16),
     "sym_bug_one_leader": (3, 2, 3, 1, 3, 1, 1, 2, 1, 0),
+    # SYMMETRY beyond MaxLogLen 1 / MaxDup 1 / three messages (logs of 2, counts of 2, the 8-slot bag)
+    "sym_msgs5_dup2_prefix11": (3, 2, 3, 2, 5, 2, 0, 1, 1, 11),
+    "s4_sym_msgs5_prefix10": (4, 2, 3, 2, 5, 2, 0, 1, 1, 10),
+    "s5_sym_log2_dup2_prefix10": (5, 2, 3, 2, 5, 2, 0, 1, 1, 10),
     # config 3, wider bounds (specs/MCraft5Wide.cfg): the first 9 levels
     "s5_wide_prefix9": (5, 2, 3, 2, 4, 1, 0, 1, 0, 9),
     # 3-entry logs with 2 values: an RVP's mlog then fills the message's top bit

@@ -53,7 +53,8 @@ def test_kat_first_levels():
 
 BFS_CASES = ["bounded_full", "tiny2", "messages_tiny2", "elections_small", "tiny2_v2", "small", "small_sym", "s3_v1_msgs1", "bounded_prefix14",
              "bounded_sym_prefix16", "msgs5_dup2_prefix9", "s4_prefix10", "s5_prefix9", "isprefix_small",
-             "isprefix_s3v1_log2", "s4_sym_prefix16", "s5_sym_prefix16", "tiny2_log3", "s3_log3_prefix14"]
+             "isprefix_s3v1_log2", "s4_sym_prefix16", "s5_sym_prefix16", "tiny2_log3", "s3_log3_prefix14",
+             "sym_msgs5_dup2_prefix11", "s4_sym_msgs5_prefix10", "s5_sym_log2_dup2_prefix10"]
 
 
 @pytest.mark.parametrize("name", BFS_CASES)
@@ -237,7 +238,7 @@ def test_set_epochs_checkpoint_of_a_later_run_recovers(tmp_path):
 
 
 @pytest.mark.parametrize("name", ["small", "s5_prefix9", "bug_log_matching", "bounded_full", "small_sym",
-                                  "s4_sym_prefix16", "sym_bug_one_leader"])
+                                  "s4_sym_prefix16", "sym_bug_one_leader", "s4_sym_msgs5_prefix10"])
 def test_full_state_verification_is_exact(name):
     """RMC_FLAG_VERIFY_STATES: every fingerprint hit is compared with the stored
     state; with 64-bit fingerprints no hit differs, so the counts are certified
@@ -327,12 +328,17 @@ def test_expand_matches_oracle_at_capacity_edges(k):
     compare_expand(m, [random_state_edge(m, rng) for _ in range(800)])
 
 
-def compare_expand(m, states):
+def compare_expand(m, states, symmetry=False, ck=None):
+    """Returns {in-CONSTRAINT successor: its fingerprint} (under symmetry the canonical
+    key) and the successor records.  ck: a ctx of the model to use."""
     cfg = rmc.make_config(n_servers=m.n_servers, n_values=m.n_values, max_term=m.max_term,
                           max_log_len=m.max_log, max_msgs=m.max_msgs, max_dup=m.max_dup,
-                          bug_quorum=m.bug_quorum, state_capacity=1 << 12)
-    with rmc.Checker(cfg) as ck:
+                          bug_quorum=m.bug_quorum, symmetry=symmetry, state_capacity=1 << 12)
+    if ck is not None:
         out = ck.expand([to_view(m, s) for s in states])
+    else:
+        with rmc.Checker(cfg) as own:
+            out = own.expand([to_view(m, s) for s in states])
     gpu_gen = defaultdict(Counter)
     gpu_in = defaultdict(Counter)
     fps = {}
@@ -352,6 +358,7 @@ def compare_expand(m, states):
                 ora_in[(f, t)] += 1
         assert gpu_gen[idx] == ora_gen, (idx, s)
         assert gpu_in[idx] == ora_in, (idx, s)
+    return fps, out
 
 
 CLI = os.path.join(os.path.dirname(os.path.dirname(__file__)), "raft.tla_amd", "bin", "rmc-tlc")

@@ -24,9 +24,10 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 11 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 12 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
-                              rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys */
+                              rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys; 12: RMC_FLAG_CONTINUE,
+                              rmc_violations, rmc_get_violations, rmc_trace_violation */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -116,6 +117,14 @@ extern "C" {
                                            /* with rmc_get_coverage.  Single GPU, both     */
                                            /* layouts; no checkpoint / recover; ignored by */
                                            /* rmc_simulate                                 */
+/* (bit 10 is not assigned: rmc_create refuses it as an unknown flag bit) */
+#define RMC_FLAG_CONTINUE (1u << 11)       /* continue past violations (TLC -continue): a  */
+                                           /* violated invariant does not stop rmc_run_bfs; */
+                                           /* violating states are stored and expanded, and */
+                                           /* counted per invariant (rmc_get_violations).   */
+                                           /* Single GPU; the wide layout without           */
+                                           /* RMC_FLAG_SPILL only; no checkpoint / recover; */
+                                           /* ignored by rmc_simulate                       */
 
 /* rmc_config.invariants — the INVARIANT names the engine knows (fused checks).
  * TypeOK on the packed layout: the search (rmc_run_bfs, rmc_simulate) evaluates
@@ -291,7 +300,7 @@ const char* rmc_version(void);                    /* "rmc <abi> gfx950 ..."     
  * Replaces TLC's BFS worker loop (ModelChecker: dequeue, getNextStates over
  * Next raft.tla:421-430, CONSTRAINT filter, FP64 + FPSet.put, invariant check,
  * enqueue).  Blocks until fixpoint, first violation, deadlock (when checked),
- * max_depth, or the callback asks to stop. */
+ * max_depth, or the callback asks to stop (RMC_FLAG_CONTINUE: not at a violation). */
 int rmc_run_bfs(rmc_ctx* ctx, rmc_progress_fn cb, void* user);
 /* Changes rmc_config.seed (fingerprint salt) for the next run on this ctx. */
 int rmc_set_seed(rmc_ctx* ctx, uint64_t seed);
@@ -337,6 +346,45 @@ typedef struct rmc_coverage {
 } rmc_coverage;
 int rmc_get_coverage(const rmc_ctx* ctx, rmc_coverage* out);
 const char* rmc_coverage_action(int32_t row);
+
+/* ---- continue past violations (TLC -continue) --------------------------------
+ * With RMC_FLAG_CONTINUE a violated invariant does not stop rmc_run_bfs: the
+ * violating states are stored and expanded like any other, and the run ends at
+ * fixpoint, at max_depth, on a callback stop, or on a deadlock (handled as
+ * without the flag).  rmc_result's generated, distinct, depth, left_on_queue and
+ * the level callbacks are those of the same model with no violated invariant in
+ * its mask; violated_inv and violation_depth are what the run without the flag
+ * reports — the first level with a violation and its least index — and
+ * rmc_trace traces to that state.
+ * rmc_get_violations: the tallies over every stored state, all deterministic
+ * (the set of stored states is; under SYMMETRY the predicates are
+ * permutation-invariant, so whichever member of an orbit is stored counts the
+ * same).  RMC_E_STATE on a ctx without the flag or before a run; every
+ * rmc_run_bfs starts from zero tallies.
+ * rmc_trace_violation: rmc_trace to the least-index stored state that violates
+ * `inv_bit` — one RMC_INV_* bit of the ctx's mask — checked alone: *len is
+ * depth[r] and the last state violates that invariant (which state it is may
+ * differ between runs; its depth does not).  RMC_E_STATE when each[r] == 0,
+ * RMC_E_INVAL for a bit outside the mask.
+ * The counting is a pass of its own after each expansion launch (the expansion
+ * kernels are unchanged); without the flag nothing is allocated, launched or
+ * read back for it.  Packed layout: resident, RMC_FLAG_SPILL (both windows),
+ * SYMMETRY, RMC_FLAG_VERIFY_STATES, RMC_FLAG_COVERAGE.  Wide layout: resident
+ * only — with RMC_FLAG_SPILL rmc_create is RMC_E_INVAL (the ring does not store
+ * the last level of a max_depth run, so no pass can read it).  rmc_shard on a
+ * ctx with the flag is RMC_E_INVAL, rmc_checkpoint and rmc_recover RMC_E_STATE
+ * (the tallies are of whole runs and are not written). */
+#define RMC_INV_COUNT 10
+typedef struct rmc_violations {
+    uint64_t states;                /* stored states violating at least one invariant of the mask */
+    uint64_t first[RMC_INV_COUNT];  /* ... whose first violated invariant (lowest bit; the notion of
+                                       rmc_result.violated_inv / rmc_check_states) is bit r: sums to states */
+    uint64_t each[RMC_INV_COUNT];   /* ... that violate invariant r checked alone (each[r] >= first[r]) */
+    int32_t  depth[RMC_INV_COUNT];  /* level of the shallowest state violating r alone; 0 = none */
+} rmc_violations;
+int rmc_get_violations(const rmc_ctx* ctx, rmc_violations* out);
+int rmc_trace_violation(rmc_ctx* ctx, uint32_t inv_bit, rmc_state_view* states, int32_t* families,
+                        int32_t* instances, size_t cap, size_t* len);
 
 /* Counterexample: the states from an initial state to the violating (or
  * deadlocked) state, in order, with the action family and lane of the step

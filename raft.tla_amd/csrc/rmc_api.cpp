@@ -15,6 +15,7 @@
 
 #include "rmc_cover.h"
 #include "rmc_ctx.h"
+#include "rmc_viol.h"
 
 using namespace rmc;
 
@@ -34,7 +35,7 @@ int validate(const rmc_config* c, std::string* why) {
     if (c->n_servers < 2 || c->n_servers > RMC_MAX_SERVERS) return bad("n_servers must be 2..5");
     if (c->n_values < 1 || c->n_values > RMC_MAX_VALUES) return bad("n_values must be 1..2");
     if (c->invariants & ~1023u) return bad("unknown invariant bit");
-    if (c->flags & ~1023u) return bad("unknown flag bit");
+    if (c->flags & ~(1023u | RMC_FLAG_CONTINUE)) return bad("unknown flag bit");  // (bit 10 is not assigned)
     if ((c->flags & RMC_UNBOUNDED_ANY) && c->max_depth <= 0)
         return bad("a model with unbounded fields (RMC_FLAG_UNBOUNDED_*) needs max_depth > 0 (TLC -depth)");
     if (wide_wanted(*c)) return validate_wide(c, why);  // bounds beyond the packed capacity
@@ -157,6 +158,36 @@ int cover_end(rmc_ctx* c) {
     return 0;
 }
 
+static_assert(VIOL_INVS == RMC_INV_COUNT, "rmc_viol.h's invariants are rmc.h's");
+
+int viol_begin(rmc_ctx* c) {
+    c->viol_valid = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_viol, 0, VIOL_LEAST * 8, c->st));
+    HIPCHK(c, hipMemsetAsync(c->d_viol + VIOL_LEAST, 0xFF, VIOL_INVS * 8, c->st));
+    return 0;
+}
+
+int viol_end(rmc_ctx* c) {
+    unsigned long long h[VIOL_WORDS];
+    HIPCHK(c, hipMemcpyAsync(h, c->d_viol, sizeof h, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    rmc_violations& v = c->viol;
+    v = rmc_violations{};
+    for (int r = 0; r < VIOL_INVS; ++r) {
+        v.first[r] = h[VIOL_FIRST + r];
+        v.each[r] = h[VIOL_EACH + r];
+        v.states += v.first[r];
+        const u64 least = h[VIOL_LEAST + r];
+        c->viol_least[r] = least;
+        if (least == ~0ull) continue;
+        // level d = [level_start[d - 1], level_start[d])
+        const auto it = std::upper_bound(c->level_start.begin(), c->level_start.end(), least);
+        v.depth[r] = (int32_t)(it - c->level_start.begin());
+    }
+    c->viol_valid = 1;
+    return 0;
+}
+
 int level_error(rmc_ctx* c, const Counters& k, int depth, const LevelText& text, int rank) {
     const std::string on = rank < 0 ? "" : " on rank " + std::to_string(rank);
     if (k.table_full) return fail(c, RMC_E_CAPACITY, "fingerprint set full" + on);
@@ -180,14 +211,18 @@ void scan_target(rmc_ctx* c, const Counters* rows, int n, int depth) {
             c->res.violated_inv = 1 << (int)(rows[r].viol & 15);
             c->res.violation_depth = depth;
             c->have_target = 1;
+            c->stop = continue_on(c) ? 0 : 1;
             c->target_idx = ((u64)r << 48) | (rows[r].viol >> 4);
         }
     if (c->cfg.flags & RMC_FLAG_CHECK_DEADLOCK)
-        for (int r = 0; r < n && !c->have_target; ++r)
+        for (int r = 0; r < n && !c->stop; ++r)
             if (rows[r].deadlock != ~0ull) {
                 c->res.deadlock = 1;
-                c->have_target = 1;
-                c->target_idx = ((u64)r << 48) | rows[r].deadlock;
+                c->stop = 1;
+                if (!c->have_target) {  // (RMC_FLAG_CONTINUE: a violation recorded before stays the target)
+                    c->have_target = 1;
+                    c->target_idx = ((u64)r << 48) | rows[r].deadlock;
+                }
             }
 }
 
@@ -294,6 +329,10 @@ int rmc_create(const rmc_config* cfg, rmc_ctx** out) {
     memset(c->h_ctr, 0, sizeof(Counters));
     if (cover_on(c) && hipMalloc(&c->d_cov, sizeof(rmc_coverage)) != hipSuccess) {
         c->err = "device allocation failed (coverage tallies)";
+        return bail(RMC_E_NOMEM);
+    }
+    if (continue_on(c) && hipMalloc(&c->d_viol, VIOL_WORDS * 8) != hipSuccess) {
+        c->err = "device allocation failed (violation tallies)";
         return bail(RMC_E_NOMEM);
     }
     if (c->wide) {  // bounds beyond the packed capacity: the wide layout (rmc_wide.cpp)
@@ -408,6 +447,7 @@ void rmc_destroy(rmc_ctx* c) {
     if (c->spill.hs_bytes) munmap(c->spill.h_state, c->spill.hs_bytes);
     (void)hipFree(c->B.ties);
     (void)hipFree(c->d_cov);
+    (void)hipFree(c->d_viol);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -433,6 +473,8 @@ static int start_run(rmc_ctx* c, int* depth) {
     if (int rc = reset_counters(c, false)) return rc;
     if (cover_on(c))
         if (int rc = cover_begin(c)) return rc;
+    if (continue_on(c))
+        if (int rc = viol_begin(c)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
@@ -444,6 +486,8 @@ static int start_run(rmc_ctx* c, int* depth) {
     if (c->sh.verify) HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, 0, c->h_ctr->count, c->st));
     if (cover_on(c))  // row Init: the one initial state generated, and what the seed stored
         HIPCHK(c, c->k->cover(c->P, c->B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
+    if (continue_on(c))  // the seed's states
+        HIPCHK(c, c->k->violations(c->P, c->B, 0, c->h_ctr->count, c->d_viol, c->st));
     return 0;
 }
 
@@ -456,8 +500,11 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool resume = c->resume != 0;  // rmc_recover restored store, set and counters
     c->resume = 0;
     c->have_target = 0;
+    c->stop = 0;
     c->cov_valid = 0;
-    const bool cover = cover_on(c);  // (rmc_recover refuses the flag: never a resumed run)
+    c->viol_valid = 0;
+    const bool cover = cover_on(c);  // (rmc_recover refuses the flags: never a resumed run)
+    const bool cont = continue_on(c);
     int depth = 0;
     if (resume) {
         c->res.left_on_queue = 0;
@@ -480,7 +527,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     }();
     const LevelText text = {"verification: a stored state has no fingerprint slot", "symmetry tie buffer full", "states",
                             &c->walked};
-    for (int more = 1; more && !c->have_target;) {
+    for (int more = 1; more && !c->stop;) {
         const u64 lo = c->level_start[depth - 1], hi = c->level_start[depth];
         if (lo == hi) break;  // fixpoint
         if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
@@ -567,16 +614,19 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     c->res.spills = cnt / win;  // passes of the ring
                 }
             }
-            if (cover) {
+            if (cover || cont) {
                 // the coverage pass of this launch: its parents [a, b) are still resident
                 // (the store; the linear window, which moves only [base, a) and before the
                 // launch; the ring, whose room is relative to a), and the states it added
-                // are [count before, count after) — after k_ties, Publish / Verify
+                // are [count before, count after) — after k_ties, Publish / Verify.  The
+                // violation pass reads those states: resident too (ring_room keeps a
+                // launch's new states inside the window)
                 if (!c->sh.verify && !c->spill.on) {  // (those paths have read the counters)
                     if (int rc = read_counters(c)) return rc;
                     if (c->h_ctr->overflow || c->h_ctr->table_full) break;
                 }
-                HIPCHK(c, c->k->cover(c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+                if (cover) HIPCHK(c, c->k->cover(c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+                if (cont) HIPCHK(c, c->k->violations(c->P, c->B, cov_before, c->h_ctr->count, c->d_viol, c->st));
             }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
@@ -586,6 +636,8 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->res.verified_spilled = c->spill.host_hits;
     if (cover)
         if (int rc = cover_end(c)) return rc;
+    if (cont)
+        if (int rc = viol_end(c)) return rc;
     const double D = (double)c->res.distinct, G = (double)c->res.generated;
     // TLC's "calculated (optimistic)" fingerprint-collision estimate
     c->res.collision_probability = fp_collision_estimate(D, G, c->table_slots, c->set_epoch != 0);
@@ -629,25 +681,35 @@ const char* rmc_coverage_action(int32_t row) {
     return row >= 0 && row < RMC_COV_ACTIONS ? kRows[row] : nullptr;
 }
 
+int rmc_get_violations(const rmc_ctx* c, rmc_violations* out) {
+    if (!c || !out) return RMC_E_INVAL;
+    rmc_ctx* m = const_cast<rmc_ctx*>(c);  // (only the message is written)
+    if (!continue_on(c)) return fail(m, RMC_E_STATE, "rmc_get_violations: the ctx was created without RMC_FLAG_CONTINUE");
+    if (!c->viol_valid) return fail(m, RMC_E_STATE, "rmc_get_violations: no completed rmc_run_bfs to report");
+    *out = c->viol;
+    return 0;
+}
+
 int rmc_get_result(const rmc_ctx* c, rmc_result* out) {
     if (!c || !out) return RMC_E_INVAL;
     *out = c->res;
     return 0;
 }
 
-// The counterexample: parent links back to Init, then the states.  States
-// whose store was spilled are re-derived by replaying the recorded lanes from
-// the last state still known (Init at worst) with the listing kernel — the
-// stored successor of a parent through a lane is exactly what it lists.
-int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap, size_t* len) {
-    if (!c || !len) return RMC_E_INVAL;
-    if (!c->have_target) return fail(c, RMC_E_STATE, "no violation or deadlock to trace");
+}  // extern "C"
+
+// The counterexample to the single-GPU state `target`: parent links back to Init,
+// then the states.  States whose store was spilled are re-derived by replaying the
+// recorded lanes from the last state still known (Init at worst) with the listing
+// kernel — the stored successor of a parent through a lane is exactly what it lists.
+static int trace_to(rmc_ctx* c, u64 target, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
+                    size_t* len) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->wide) return trace_wide(c, states, families, instances, cap, len);
-    if (c->dist.on) return trace_sharded(c, states, families, instances, cap, len);
+    if (c->wide) return trace_wide(c, target, states, families, instances, cap, len);
     std::vector<u64> chain;
     std::vector<uint8_t> acts;
-    if (int rc = walk_links(c, [c](u64 i, u64* p, uint8_t* a) { return read_link(c, i, p, a); }, &chain, &acts)) return rc;
+    if (int rc = walk_links(c, target, [c](u64 i, u64* p, uint8_t* a) { return read_link(c, i, p, a); }, &chain, &acts))
+        return rc;
     *len = chain.size();
     const u64 NW = (u64)c->NW, RW = 6 + NW, lanes = (u64)c->P.off[10];
     std::vector<u32> cur(NW);
@@ -688,6 +750,31 @@ int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* in
         }
     }
     return 0;
+}
+
+extern "C" {
+
+int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap, size_t* len) {
+    if (!c || !len) return RMC_E_INVAL;
+    if (!c->have_target) return fail(c, RMC_E_STATE, "no violation or deadlock to trace");
+    if (c->dist.on && !c->wide) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        return trace_sharded(c, states, families, instances, cap, len);
+    }
+    return trace_to(c, c->target_idx, states, families, instances, cap, len);
+}
+
+int rmc_trace_violation(rmc_ctx* c, uint32_t inv_bit, rmc_state_view* states, int32_t* families, int32_t* instances,
+                        size_t cap, size_t* len) {
+    if (!c || !len) return RMC_E_INVAL;
+    if (!continue_on(c))
+        return fail(c, RMC_E_STATE, "rmc_trace_violation: the ctx was created without RMC_FLAG_CONTINUE");
+    if (!inv_bit || (inv_bit & (inv_bit - 1)) || !(inv_bit & c->cfg.invariants))
+        return fail(c, RMC_E_INVAL, "rmc_trace_violation: inv_bit must be one RMC_INV_* bit of the ctx's invariants");
+    if (!c->viol_valid) return fail(c, RMC_E_STATE, "rmc_trace_violation: no completed rmc_run_bfs to report");
+    const int r = __builtin_ctz(inv_bit);
+    if (!c->viol.each[r]) return fail(c, RMC_E_STATE, "rmc_trace_violation: no stored state violates this invariant");
+    return trace_to(c, c->viol_least[r], states, families, instances, cap, len);
 }
 
 }  // extern "C"

@@ -78,6 +78,9 @@ int rmc_checkpoint(rmc_ctx* c, const char* path) {
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_COVERAGE (the tallies are of whole "
                                     "runs and are not written)");
+    if (c->cfg.flags & RMC_FLAG_CONTINUE)
+        return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_CONTINUE (the violation tallies are of "
+                                    "whole runs and are not written)");
     if (c->level_start.size() < 2 || c->have_target)
         return fail(c, RMC_E_STATE, "checkpoint: needs a BFS stopped at a level boundary without a violation");
     if (c->res.left_on_queue == 0) return fail(c, RMC_E_STATE, "checkpoint: the search is complete");
@@ -132,6 +135,9 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_COVERAGE (the tallies are of whole runs)");
+    if (c->cfg.flags & RMC_FLAG_CONTINUE)
+        return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_CONTINUE (the violation tallies are of "
+                                    "whole runs)");
     if (c->spill.on && c->sh.verify)
         return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_VERIFY_STATES and RMC_FLAG_SPILL");
     HIPCHK(c, hipSetDevice(c->cfg.device));

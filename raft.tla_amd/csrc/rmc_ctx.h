@@ -148,10 +148,18 @@ struct rmc_ctx {
     unsigned long long* d_cov = nullptr;
     rmc_coverage cov{};
     int cov_valid = 0;
+    // continue past violations (RMC_FLAG_CONTINUE; rmc_viol.h): the device tallies (VIOL_WORDS
+    // words: first, each, least index), allocated only with the flag, the last completed run's
+    // result (rmc_get_violations) and its least indices (rmc_trace_violation)
+    unsigned long long* d_viol = nullptr;
+    rmc_violations viol{};
+    rmc::u64 viol_least[RMC_INV_COUNT] = {};
+    int viol_valid = 0;
     rmc_result res{};
     std::string err;
     std::vector<rmc::u64> level_start;  // level d (1-based) = [level_start[d-1], level_start[d])
     int have_target = 0;                // a violation / deadlock state to trace
+    int stop = 0;                       // ... that ends the search (RMC_FLAG_CONTINUE: a deadlock only)
     rmc::u64 target_idx = 0;            // sharded: global ref (rank << 48 | index)
     DistState dist;
     SpillState spill;
@@ -200,6 +208,12 @@ int seed_init(rmc_ctx* c);
 inline bool cover_on(const rmc_ctx* c) { return (c->cfg.flags & RMC_FLAG_COVERAGE) != 0; }
 int cover_begin(rmc_ctx* c);
 int cover_end(rmc_ctx* c);
+// Continue past violations, both layouts: the tallies cleared at the start of a
+// run (the least indices to ~0), and at its end copied out and turned into
+// rmc_violations (depth[r]: the level of level_start that holds the least index).
+inline bool continue_on(const rmc_ctx* c) { return (c->cfg.flags & RMC_FLAG_CONTINUE) != 0; }
+int viol_begin(rmc_ctx* c);
+int viol_end(rmc_ctx* c);
 // After the seed launch's read_counters, on either layout: level 1 is the states
 // it stored, and an invariant Init violates is the target.  Returns the depth.
 int seed_done(rmc_ctx* c);
@@ -216,7 +230,9 @@ struct LevelText {
 int level_error(rmc_ctx* c, const rmc::Counters& k, int depth, const LevelText& text, int rank);
 // The violation, else deadlock (RMC_FLAG_CHECK_DEADLOCK), the counter rows of n
 // ranks report, as the target to trace (target_idx = rank << 48 | index; the
-// lowest rank's wins); nothing if a target is already known.
+// lowest rank's wins); nothing if a target is already known.  Either one stops
+// the search (c->stop) — under RMC_FLAG_CONTINUE only the deadlock does: the
+// first violation is recorded once, stays the target, and the search goes on.
 void scan_target(rmc_ctx* c, const rmc::Counters* rows, int n, int depth);
 // The end of a level's launches (hi: the states before it), from the closing
 // event to the progress callback: kernel time, the Counters.overflow errors,
@@ -253,7 +269,8 @@ int validate_wide(const rmc_config* c, std::string* why);
 int create_wide(rmc_ctx* c);
 void destroy_wide(rmc_ctx* c);
 int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user);
-int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap, size_t* len);
+int trace_wide(rmc_ctx* c, rmc::u64 target, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
+               size_t* len);
 int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view* out, size_t cap, size_t* n_out);
 int check_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t mask, int32_t* violated);
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, rmc::i64 rec_beh,
@@ -310,11 +327,11 @@ inline void fill_sim_result(rmc_sim_result* out, const rmc::SimCounters& h, rmc:
     out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// The counterexample's parent links from the target back to an initial state, then
+// The counterexample's parent links from `target` back to an initial state, then
 // reversed: read_one(idx, &parent, &act) reads one link.
 template <class F>
-int walk_links(rmc_ctx* c, F read_one, std::vector<rmc::u64>* chain, std::vector<uint8_t>* acts) {
-    for (rmc::u64 idx = c->target_idx;;) {
+int walk_links(rmc_ctx* c, rmc::u64 target, F read_one, std::vector<rmc::u64>* chain, std::vector<uint8_t>* acts) {
+    for (rmc::u64 idx = target;;) {
         rmc::u64 p = 0;
         uint8_t a = 0;
         if (int rc = read_one(idx, &p, &a)) return rc;

@@ -7,6 +7,9 @@
 //  k_cover  : action coverage (RMC_FLAG_COVERAGE, TLC -coverage): a pass beside
 //             each expansion launch that tallies the enabled lanes of its
 //             parents and the producing lanes of its new states per action.
+//  k_violations : continue past violations (RMC_FLAG_CONTINUE, TLC -continue): a
+//             pass over the states each launch added that tallies, per
+//             invariant, the stored states violating it.
 //
 // and k_rehash (recovery), k_pack_rep (replicated levels), k_check (rmc_check_states),
 // k_keys (rmc_state_keys), k_simulate (TLC -simulate).
@@ -20,6 +23,7 @@
 #include "rmc_dev_state.h"
 #include "rmc_dev_verify.h"
 #include "rmc_internal.h"
+#include "rmc_viol.h"
 
 namespace rmc {
 
@@ -260,6 +264,72 @@ __global__ __launch_bounds__(256) void k_cover(const Params P, const DevBufs B, 
         u64 v = s_row[threadIdx.x];
         if (threadIdx.x == COV_INIT && blockIdx.x == 0) v += n_init;
         if (v) atomicAdd(&cov[threadIdx.x], (unsigned long long)v);
+    }
+}
+
+// ---- continue past violations (RMC_FLAG_CONTINUE, TLC -continue; rmc_viol.h) ---------
+// A pass of its own over the states one launch (or the seed) added, [nlo, nhi),
+// which every allowed path still holds (the store; the linear window, which moves
+// only expanded states and before a launch; the ring, whose room keeps a launch's
+// new states inside it): each state is loaded through wslot and classified by
+// classify_violations — the BFS's own check for `first`, each remaining bit of
+// the mask alone for `each`.  Reduced like k_cover: per-thread counts in registers
+// (every index a compile-time constant), a wave sum, one LDS add per wave and
+// row, one global atomic per block and non-zero row; the least index per
+// invariant through a wave min and one atomicMin per wave that has one.
+__device__ __forceinline__ u64 wave_min64(u64 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = (u64)(u32)__shfl_xor((int)(u32)v, off) | ((u64)(u32)__shfl_xor((int)(u32)(v >> 32), off) << 32);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+template <int S, int K>
+__global__ __launch_bounds__(256) void k_violations(const Params P, const DevBufs B, u64 nlo, u64 nhi,
+                                                    unsigned long long* viol) {
+    constexpr int NW = 2 * S + K;
+    __shared__ u32 s_row[2 * VIOL_INVS];
+    if (threadIdx.x < 2 * VIOL_INVS) s_row[threadIdx.x] = 0;
+    __syncthreads();
+    u32 nf[VIOL_INVS], ne[VIOL_INVS];
+    u64 least[VIOL_INVS];
+#pragma unroll
+    for (int r = 0; r < VIOL_INVS; ++r) {
+        nf[r] = ne[r] = 0;
+        least[r] = ~0ull;
+    }
+    nhi = nhi < B.cap ? nhi : B.cap;  // (a launch that overflowed the store is an error: its tallies are not read)
+    for (u64 i = nlo + (u64)blockIdx.x * 256ull + threadIdx.x; i < nhi; i += (u64)gridDim.x * 256ull) {
+        u64 w[S];
+        u32 m[K];
+        load_state<S, K>(B.store + wslot(B, i) * (u64)NW, w, m);
+        const ViolClass c = classify_violations<S, K>(w, m, P);
+        if (!c.first) continue;
+#pragma unroll
+        for (int r = 0; r < VIOL_INVS; ++r) {
+            const bool alone = ((c.each >> r) & 1u) != 0;
+            nf[r] += c.first == r + 1 ? 1u : 0u;
+            ne[r] += alone ? 1u : 0u;
+            least[r] = alone && i < least[r] ? i : least[r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < VIOL_INVS; ++r) {
+        const u32 fs = wave_sum32(nf[r]), es = wave_sum32(ne[r]);
+        if (!es) continue;  // (wave-uniform; first[r] <= each[r])
+        const u64 lm = wave_min64(least[r]);
+        if (__lane_id() == 0) {
+            if (fs) atomicAdd(&s_row[VIOL_FIRST + r], fs);
+            atomicAdd(&s_row[VIOL_EACH + r], es);
+            atomicMin(&viol[VIOL_LEAST + r], (unsigned long long)lm);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * VIOL_INVS) {
+        const u32 v = s_row[threadIdx.x];
+        if (v) atomicAdd(&viol[threadIdx.x], (unsigned long long)v);
     }
 }
 

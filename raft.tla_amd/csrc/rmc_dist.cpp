@@ -132,6 +132,7 @@ int start(rmc_ctx* c, Run& R) {
     c->res.set_slots = c->table_slots;
     if (!resume) c->level_start.clear();
     c->have_target = 0;
+    c->stop = 0;
     D.keys_sent = D.states_sent = D.chunks = D.parked = 0;
     D.xfer_seconds = D.wait_seconds = 0;
     D.rep_levels = 0;
@@ -570,7 +571,7 @@ int run_bfs_sharded(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     // CONSTRAINT on every field (the capacity pass reads the store)
     // (a world of one has nothing to gather: its levels run as plain rounds)
     const bool rep_ok = D.world > 1 && !c->sh.verify && !c->sh.sym && !c->P.unbounded && D.rep_max > 0;
-    for (bool more = true; more && !c->have_target;) {
+    for (bool more = true; more && !c->stop;) {
         const u64 lo = c->level_start[(size_t)R.depth - 1], hi = c->level_start[(size_t)R.depth];
         D.lvl = R.depth;
         D.rnd = 0;
@@ -654,6 +655,9 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
         return fail(c, RMC_E_INVAL, "rmc_shard needs an RCCL id or a host transport");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_COVERAGE (coverage is single GPU)");
+    if (c->cfg.flags & RMC_FLAG_CONTINUE)
+        return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_CONTINUE (the violation tallies are "
+                                    "single GPU)");
     if (c->spill.on) return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_SPILL");
     if (c->wide) return fail(c, RMC_E_INVAL, "sharded mode runs the packed layout only (bounds within its capacity)");
     HIPCHK(c, hipSetDevice(c->cfg.device));

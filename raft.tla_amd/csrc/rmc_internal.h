@@ -140,6 +140,10 @@ struct ShapeKernels {
     // parents [lo, hi) and the states their launch added, [nlo, nhi), into cov (k_cover, rmc_dev_tools.h)
     hipError_t (*cover)(const Params& P, const DevBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
                         unsigned long long* cov, hipStream_t st);
+    // the states a launch added, [nlo, nhi), into the violation tallies (k_violations, rmc_dev_tools.h;
+    // viol: VIOL_WORDS words, rmc_viol.h)
+    hipError_t (*violations)(const Params& P, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
+                             hipStream_t st);
     hipError_t (*check)(const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
     // keys[t] = the key of in[t] (P.fp_mask applied); ref != nullptr: same[t] = in[t] compares equal to
     // the record in[ref[t]] (k_keys, rmc_dev_tools.h)
@@ -244,6 +248,9 @@ hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t
 // ShapeKernels::cover on the wide records (k_wcover)
 hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
                          unsigned long long* cov, hipStream_t st);
+// ShapeKernels::violations on the wide records (k_wviolations; the resident store only)
+hipError_t launch_wviolations(const WModel& M, const WideBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
+                              hipStream_t st);
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,

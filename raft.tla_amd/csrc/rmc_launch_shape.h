@@ -32,6 +32,17 @@ static hipError_t launch_cover_t(const Params& P, const DevBufs& B, u64 lo, u64 
     return hipGetLastError();
 }
 
+// The violation pass of one expansion launch (or of the seed step) over the states it added.
+template <int S, int K>
+static hipError_t launch_violations_t(const Params& P, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
+                                      hipStream_t st) {
+    if (nhi <= nlo) return hipSuccess;
+    const u64 blocks = (nhi - nlo + 255) / 256;
+    hipLaunchKernelGGL((k_violations<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, P, B,
+                       nlo, nhi, viol);
+    return hipGetLastError();
+}
+
 template <int S, int K>
 static hipError_t launch_check_t(const Params& P, const u32* in, u64 n, int* out, hipStream_t st) {
     if (!n) return hipSuccess;
@@ -221,6 +232,7 @@ static ShapeKernels shape_table() {
     };
     k.simulate = launch_sim_t<S, K>;
     k.cover = launch_cover_t<S, K>;
+    k.violations = launch_violations_t<S, K>;
     k.check = launch_check_t<S, K>;
     k.keys = launch_keys_t<S, K>;
     k.set_salt = set_object_salt;

@@ -174,7 +174,12 @@ int usage() {
             "usage: rmc-tlc [-config X.cfg] [-depth N] [-deadlock] [-device D] [-capacity N] [-workers N]\n"
             "               [-verify] [-fpseed S] [-checkpoint F] [-recover F] [-simulate [num=N]] [-seed S]\n"
             "               [-raft raft.tla] [-builtin-raft] [-gpus N] [-nospill] [-window N] [-fpmem B]\n"
-            "               [-coverage [minutes]] X.tla\n"
+            "               [-coverage [minutes]] [-continue] X.tla\n"
+            "  -continue      search past invariant violations (TLC -continue): violating states are kept\n"
+            "             and expanded; after the search every violated invariant is reported with the\n"
+            "             trace to its first state and the number of states that violate it (single\n"
+            "             GPU; not with -checkpoint, -recover or -simulate; a wide-layout run then\n"
+            "             keeps every state on the device, as under -nospill)\n"
             "  -coverage [M]  per-action statistics (TLC -coverage): for every action of Next the states it\n"
             "             generated and the distinct states it found; M, TLC's reporting interval in\n"
             "             minutes, is accepted and ignored (single GPU; not with -checkpoint, -recover\n"
@@ -269,7 +274,7 @@ int main(int argc, char** argv) {
     std::string ckpt, recover, raft;
     uint32_t fopts = 0;
     unsigned long long capacity = 0, window = 0, fpmem = 0;
-    int nospill = 0, coverage = 0;
+    int nospill = 0, coverage = 0, cont = 0;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : nullptr; };
@@ -282,6 +287,7 @@ int main(int argc, char** argv) {
         else if (s == "-gpus") { const char* v = next(); if (!v) return usage(); gpus = atoi(v); }
         else if (s == "-verify") verify = 1;
         else if (s == "-nospill") nospill = 1;
+        else if (s == "-continue") cont = 1;
         else if (s == "-coverage") {  // TLC's optional interval in minutes: a number, not the model
             coverage = 1;
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9' &&
@@ -318,6 +324,11 @@ int main(int argc, char** argv) {
                 gpus > 1 ? "-gpus N > 1" : !ckpt.empty() ? "-checkpoint" : !recover.empty() ? "-recover" : "-simulate");
         return usage();
     }
+    if (cont && (gpus > 1 || !ckpt.empty() || !recover.empty() || simulate)) {
+        fprintf(stderr, "-continue counts whole single-GPU searches: not with %s\n",
+                gpus > 1 ? "-gpus N > 1" : !ckpt.empty() ? "-checkpoint" : !recover.empty() ? "-recover" : "-simulate");
+        return usage();
+    }
     if (cfg.empty()) cfg = (tla.size() > 4 && tla.substr(tla.size() - 4) == ".tla" ? tla.substr(0, tla.size() - 4) : tla) + ".cfg";
     printf("rmc-tlc: %s\n", rmc_version());
     if (const char* b = getenv("RMC_BUILTIN_RAFT")) if (b[0] == '1') fopts |= RMC_FRONT_BUILTIN_RAFT;
@@ -339,14 +350,16 @@ int main(int argc, char** argv) {
     if (nodeadlock) c.flags &= ~RMC_FLAG_CHECK_DEADLOCK;
     if (verify) c.flags |= RMC_FLAG_VERIFY_STATES;
     if (coverage) c.flags |= RMC_FLAG_COVERAGE;
+    if (cont) c.flags |= RMC_FLAG_CONTINUE;
     // like TLC's states/ directory, expanded levels leave the device when it fills
     // (single GPU; under -verify the spilled states keep a host copy for the
     // comparisons, and checkpoints of such runs stay resident).  The wide layout of
     // -depth runs of unbounded models spills too, through a ring window of its
     // records with the trace links in HBM — not under -verify, which on the wide
-    // layout compares with resident records only (it refuses the two flags together)
+    // layout compares with resident records only (it refuses the two flags together),
+    // nor under -continue, whose pass reads every stored state's record
     const bool wide = rmc_state_bytes(&c) > 64 * 4;  // (a packed state is at most 18 words)
-    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && verify))
+    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && (verify || cont)))
         c.flags |= RMC_FLAG_SPILL;
     c.device_window = window;
     c.set_bytes = fpmem;
@@ -441,7 +454,7 @@ int main(int argc, char** argv) {
         rc = rmc_run_bfs(ctx, progress, nullptr);
         if (rc) { printf("Error: %s\n", rmc_last_error(ctx)); rmc_destroy(ctx); return 1; }
         rmc_get_result(ctx, &r);
-        if (r.violated_inv || r.deadlock) {
+        if ((r.violated_inv && !cont) || r.deadlock) {  // (-continue: the traces are rmc_trace_violation's)
             size_t len = 0;
             rmc_trace(ctx, nullptr, nullptr, nullptr, 0, &len);
             tr_st.resize(len);
@@ -451,9 +464,7 @@ int main(int argc, char** argv) {
         }
     }
     int exitcode = 0;
-    if (r.violated_inv || r.deadlock) {
-        if (r.violated_inv) printf("Error: Invariant %s is violated.\n", inv_name(r.violated_inv));
-        else printf("Error: Deadlock reached.\n");
+    auto print_behaviour = [&]() {
         printf("Error: The behavior up to this point is:\n");
         for (size_t k = 0; k < tr_st.size(); ++k) {
             if (tr_fam[k] < 0 || k == 0) printf("State %zu: <Initial predicate>\n", k + 1);
@@ -461,6 +472,48 @@ int main(int argc, char** argv) {
             print_state(tr_st[k]);
             printf("\n");
         }
+    };
+    rmc_violations vs{};
+    if (cont && rmc_get_violations(ctx, &vs)) {
+        printf("Error: %s\n", rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 1;
+    }
+    if (cont && (vs.states || r.deadlock)) {
+        // TLC -continue: every violated invariant, in mask order, with the trace to its first state
+        const bool dead_only = r.deadlock && !r.violated_inv;  // (its trace was fetched above)
+        std::vector<rmc_state_view> dl_st;
+        std::vector<int32_t> dl_fam, dl_inst;
+        if (dead_only) { dl_st.swap(tr_st); dl_fam.swap(tr_fam); dl_inst.swap(tr_inst); }
+        for (int q = 0; q < RMC_INV_COUNT; ++q) {
+            if (!vs.each[q]) continue;
+            printf("Error: Invariant %s is violated.\n", inv_name(1 << q));
+            size_t len = 0;
+            if (rmc_trace_violation(ctx, 1u << q, nullptr, nullptr, nullptr, 0, &len)) {
+                printf("Error: %s\n", rmc_last_error(ctx));
+                continue;
+            }
+            tr_st.resize(len);
+            tr_fam.resize(len);
+            tr_inst.resize(len);
+            if (rmc_trace_violation(ctx, 1u << q, tr_st.data(), tr_fam.data(), tr_inst.data(), len, &len)) {
+                printf("Error: %s\n", rmc_last_error(ctx));
+                continue;
+            }
+            print_behaviour();
+        }
+        if (r.deadlock) {
+            printf("Error: Deadlock reached.\n");
+            if (dead_only) {
+                tr_st.swap(dl_st); tr_fam.swap(dl_fam); tr_inst.swap(dl_inst);
+                print_behaviour();
+            }
+        }
+        exitcode = 12;
+    } else if (r.violated_inv || r.deadlock) {
+        if (r.violated_inv) printf("Error: Invariant %s is violated.\n", inv_name(r.violated_inv));
+        else printf("Error: Deadlock reached.\n");
+        print_behaviour();
         exitcode = 12;
     } else {
         printf("Model checking completed. No error has been found.\n");
@@ -474,6 +527,16 @@ int main(int argc, char** argv) {
         if (r.verified_spilled)
             printf("  (%llu of the hits were on states that had left the device window: compared with "
                    "their host copies)\n", (unsigned long long)r.verified_spilled);
+    }
+    if (cont) {
+        // a line of our own (not TLC's): per violated invariant the stored states that violate it
+        // checked alone, those it is the first violated invariant of, and its shallowest level
+        printf("Violations (-continue): %llu states violate an invariant.", (unsigned long long)vs.states);
+        for (int q = 0; q < RMC_INV_COUNT; ++q)
+            if (vs.each[q])
+                printf(" %s: each %llu, first %llu, depth %d.", inv_name(1 << q), (unsigned long long)vs.each[q],
+                       (unsigned long long)vs.first[q], vs.depth[q]);
+        printf("\n");
     }
     if (coverage) {
         rmc_coverage cv;

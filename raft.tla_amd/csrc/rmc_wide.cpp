@@ -45,6 +45,11 @@ int validate_wide(const rmc_config* c, std::string* why) {
     if ((c->flags & RMC_FLAG_VERIFY_STATES) && (c->flags & RMC_FLAG_SPILL))
         return bad("the wide layout (bounds beyond the packed capacity) supports RMC_FLAG_VERIFY_STATES only "
                    "without RMC_FLAG_SPILL: verification needs every state resident");
+    // the ring does not store the last level of a max_depth run, so no pass can read it
+    if ((c->flags & RMC_FLAG_CONTINUE) && (c->flags & RMC_FLAG_SPILL))
+        return bad("the wide layout (bounds beyond the packed capacity) supports RMC_FLAG_CONTINUE only "
+                   "without RMC_FLAG_SPILL: the violation pass reads every stored state, and the ring "
+                   "stores no record of a depth-bounded run's last level");
     return 0;
 }
 
@@ -205,6 +210,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     WideBufs B = c->WB;
     B.salt = wide_salt(c->cfg.seed);
     c->have_target = 0;
+    c->stop = 0;
+    c->viol_valid = 0;
     c->res = rmc_result{};
     c->res.set_slots = c->table_slots;
     c->res.spill_links_on_device = B.window ? 1 : 0;
@@ -220,6 +227,9 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool cover = cover_on(c);
     if (cover)
         if (int rc = cover_begin(c)) return rc;
+    const bool cont = continue_on(c);  // (validate_wide refuses it with the ring)
+    if (cont)
+        if (int rc = viol_begin(c)) return rc;
     // Init in the record the seed kernel reads: the work record (= the store's without the ring)
     HIPCHK(c, with_record(B.window ? B.work : B.compact, [&](auto* r) {
         std::remove_pointer_t<decltype(r)> init;
@@ -232,6 +242,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     int depth = seed_done(c);
     if (cover)  // row Init: the one initial state generated, and what the seed stored
         HIPCHK(c, launch_wcover(c->WM, B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
+    if (cont)  // the seed's states
+        HIPCHK(c, launch_wviolations(c->WM, B, 0, c->h_ctr->count, c->d_viol, c->st));
     const u64 CHUNK = 1ull << 22;
     const u64 bound = wide_new_per_state(c->cfg, B.work);
     u64 records = c->h_ctr->count;  // ring: records written so far
@@ -241,7 +253,7 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const u64 vlanes = (u64)c->WM.L.off[7] + 3 * wide_bag(c->cfg, B.work);
     const u64 chunk = B.verify ? std::max<u64>(1, std::min(CHUNK, B.vcap / vlanes)) : CHUNK;
     const LevelText text = {"verification: a fingerprint hit has no stored owner", nullptr, "wide states", nullptr};
-    for (int more = 1; more && !c->have_target;) {
+    for (int more = 1; more && !c->stop;) {
         const u64 lo = c->level_start[(size_t)depth - 1], hi = c->level_start[(size_t)depth];
         if (lo == hi) break;
         if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
@@ -290,15 +302,18 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 c->res.spilled = records > B.window ? records - B.window : 0;
                 c->res.spills = records / B.window;  // passes of the ring
             }
-            if (cover) {
+            if (cover || cont) {
                 // the coverage pass of this launch: the ring still holds its parents [a, b)
                 // (its room is relative to a), and the states it added, [count before, count
-                // after), have their links even on the unstored last level
+                // after), have their links even on the unstored last level; the violation
+                // pass reads those states' records (the resident store only)
                 if (!B.verify && !B.window) {  // (those paths have read the counters)
                     if (int rc = read_counters(c)) return rc;
                     if (c->h_ctr->overflow || c->h_ctr->table_full) break;
                 }
-                HIPCHK(c, launch_wcover(c->WM, B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+                if (cover)
+                    HIPCHK(c, launch_wcover(c->WM, B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
+                if (cont) HIPCHK(c, launch_wviolations(c->WM, B, cov_before, c->h_ctr->count, c->d_viol, c->st));
             }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
@@ -308,13 +323,16 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->res.stored_here = c->res.distinct;
     if (cover)
         if (int rc = cover_end(c)) return rc;
+    if (cont)
+        if (int rc = viol_end(c)) return rc;
     const double Dd = (double)c->res.distinct, G = (double)c->res.generated;
     c->res.collision_probability = fp_collision_estimate(Dd, G, (c->WB.tmask + 1));
     c->res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
-int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap, size_t* len) {
+int trace_wide(rmc_ctx* c, u64 target, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
+               size_t* len) {
     std::vector<u64> chain;
     std::vector<uint8_t> acts;
     auto read_one = [c](u64 idx, u64* p, uint8_t* a) {
@@ -322,7 +340,7 @@ int trace_wide(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* i
         HIPCHK(c, hipMemcpy(a, c->WB.act + idx, 1, hipMemcpyDeviceToHost));
         return 0;
     };
-    if (int rc = walk_links(c, read_one, &chain, &acts)) return rc;
+    if (int rc = walk_links(c, target, read_one, &chain, &acts)) return rc;
     *len = chain.size();
     const int S = c->WM.S;
     if (c->WB.window) {

@@ -12,6 +12,7 @@
 #include "raft_wide.h"
 #include "rmc_cover.h"
 #include "rmc_internal.h"
+#include "rmc_viol.h"
 
 namespace rmc {
 namespace wide {
@@ -307,6 +308,64 @@ __global__ __launch_bounds__(256) void k_wcover(const WModel M, const WideBufs B
         u64 v = s_row[threadIdx.x];
         if (threadIdx.x == COV_INIT && blockIdx.x == 0) v += n_init;
         if (v) atomicAdd(&cov[threadIdx.x], (unsigned long long)v);
+    }
+}
+
+// Continue past violations (RMC_FLAG_CONTINUE; rmc_viol.h, the packed k_violations'
+// twin): a pass over the states one launch (or the seed) added, [nlo, nhi), on
+// the store's record in place — the resident store only (rmc_create refuses the
+// ring: it does not store the last level of a depth-bounded run).  Classified by
+// wclassify_violations, reduced as there.
+__device__ __forceinline__ u64 w_wave_min(u64 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = (u64)(u32)__shfl_xor((int)(u32)v, off) | ((u64)(u32)__shfl_xor((int)(u32)(v >> 32), off) << 32);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+template <class Store>
+__global__ __launch_bounds__(256) void k_wviolations(const WModel M, const WideBufs B, u64 nlo, u64 nhi,
+                                                     unsigned long long* viol) {
+    __shared__ u32 s_row[2 * VIOL_INVS];
+    if (threadIdx.x < 2 * VIOL_INVS) s_row[threadIdx.x] = 0;
+    __syncthreads();
+    u32 nf[VIOL_INVS], ne[VIOL_INVS];
+    u64 least[VIOL_INVS];
+#pragma unroll
+    for (int r = 0; r < VIOL_INVS; ++r) {
+        nf[r] = ne[r] = 0;
+        least[r] = ~0ull;
+    }
+    const Store* store = static_cast<const Store*>(B.store);
+    nhi = nhi < B.cap ? nhi : B.cap;  // (a launch that overflowed the store is an error: its tallies are not read)
+    for (u64 i = nlo + (u64)blockIdx.x * 256ull + threadIdx.x; i < nhi; i += (u64)gridDim.x * 256ull) {
+        const ViolClass c = wclassify_violations(M, store[i]);
+        if (!c.first) continue;
+#pragma unroll
+        for (int r = 0; r < VIOL_INVS; ++r) {
+            const bool alone = ((c.each >> r) & 1u) != 0;
+            nf[r] += c.first == r + 1 ? 1u : 0u;
+            ne[r] += alone ? 1u : 0u;
+            least[r] = alone && i < least[r] ? i : least[r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < VIOL_INVS; ++r) {
+        const u32 fs = w_wave_sum32(nf[r]), es = w_wave_sum32(ne[r]);
+        if (!es) continue;  // (wave-uniform; first[r] <= each[r])
+        const u64 lm = w_wave_min(least[r]);
+        if (__lane_id() == 0) {
+            if (fs) atomicAdd(&s_row[VIOL_FIRST + r], fs);
+            atomicAdd(&s_row[VIOL_EACH + r], es);
+            atomicMin(&viol[VIOL_LEAST + r], (unsigned long long)lm);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * VIOL_INVS) {
+        const u32 v = s_row[threadIdx.x];
+        if (v) atomicAdd(&viol[threadIdx.x], (unsigned long long)v);
     }
 }
 
@@ -738,6 +797,16 @@ hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64
         hipLaunchKernelGGL((k_wcover<Store, Ring>), grid, dim3(256), 0, st, M, B, lo, hi, nlo, nhi, n_init, cov);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+hipError_t launch_wviolations(const WModel& M, const WideBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
+                              hipStream_t st) {
+    if (nhi <= nlo) return hipSuccess;
+    if (B.window) return hipErrorInvalidValue;  // the resident store only
+    const dim3 grid(grid_for(nhi - nlo, 256, 4096));
+    if (B.compact == 2) hipLaunchKernelGGL(k_wviolations<WStateD>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
+    else if (B.compact) hipLaunchKernelGGL(k_wviolations<WStateC>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
+    else hipLaunchKernelGGL(k_wviolations<WState>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
+    return hipGetLastError();
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
                         u64 salt, hipStream_t st) {

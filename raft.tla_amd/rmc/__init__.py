@@ -34,6 +34,8 @@ INV_NAMES = {INV_TYPEOK: "TypeOK", INV_ONE_LEADER: "OneLeaderPerTerm",
 FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED = 1, 2, 4
 FLAG_UNBOUNDED_TERM, FLAG_UNBOUNDED_LOG, FLAG_UNBOUNDED_MSGS, FLAG_UNBOUNDED_DUP = 32, 64, 128, 256
 FLAG_COVERAGE = 512
+FLAG_CONTINUE = 2048  # (bit 10 is not assigned)
+INV_COUNT = 10  # RMC_INV_COUNT: the rows of rmc_violations, bit r = 1 << r
 # rows of rmc_coverage (RMC_COV_ACTIONS; rmc_coverage_action): Init, the server families, the
 # disjuncts of Receive, DuplicateMessage, DropMessage
 COVERAGE_ACTIONS = ("Init", "Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
@@ -130,6 +132,11 @@ class Coverage(C.Structure):
                 ("distinct", C.c_uint64 * len(COVERAGE_ACTIONS))]
 
 
+class Violations(C.Structure):
+    _fields_ = [("states", C.c_uint64), ("first", C.c_uint64 * INV_COUNT), ("each", C.c_uint64 * INV_COUNT),
+                ("depth", C.c_int32 * INV_COUNT)]
+
+
 class Transport(C.Structure):
     _fields_ = [("user", C.c_void_p), ("alltoallv", ALLTOALLV_FN), ("allgather", ALLGATHER_FN)]
 
@@ -140,7 +147,7 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_set_seed", "rmc_simulate", "rmc_sim_replay", "rmc_set_fp_bits",
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
            "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action",
-           "rmc_check_states", "rmc_state_keys")
+           "rmc_check_states", "rmc_state_keys", "rmc_get_violations", "rmc_trace_violation")
 
 _lib = None
 
@@ -212,6 +219,11 @@ def native():
         lib.rmc_get_coverage.restype = C.c_int
         lib.rmc_coverage_action.argtypes = [C.c_int32]
         lib.rmc_coverage_action.restype = C.c_char_p
+        lib.rmc_get_violations.argtypes = [C.c_void_p, C.POINTER(Violations)]
+        lib.rmc_get_violations.restype = C.c_int
+        lib.rmc_trace_violation.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(StateView), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.rmc_trace_violation.restype = C.c_int
         lib.rmc_check_states.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.c_uint32,
                                          C.POINTER(C.c_int32)]
         lib.rmc_check_states.restype = C.c_int
@@ -231,10 +243,10 @@ class RmcError(RuntimeError):
 def make_config(n_servers=3, n_values=2, max_term=2, max_log_len=1, max_msgs=2, max_dup=1,
                 symmetry=False, bug_quorum=False, invariants=INV_TYPEOK, check_deadlock=True,
                 device=0, max_depth=0, state_capacity=0, verify_states=False, spill=False, device_window=0,
-                set_bytes=0, coverage=False):
+                set_bytes=0, coverage=False, continue_=False):
     flags = (FLAG_SYMMETRY if symmetry else 0) | (FLAG_BUG_QUORUM if bug_quorum else 0) | \
         (FLAG_CHECK_DEADLOCK if check_deadlock else 0) | (FLAG_VERIFY_STATES if verify_states else 0) | \
-        (FLAG_SPILL if spill else 0) | (FLAG_COVERAGE if coverage else 0)
+        (FLAG_SPILL if spill else 0) | (FLAG_COVERAGE if coverage else 0) | (FLAG_CONTINUE if continue_ else 0)
     return Config(n_servers, n_values, max_term, max_log_len, max_msgs, max_dup, flags,
                   invariants, device, max_depth, state_capacity, 0, device_window, set_bytes)
 
@@ -405,6 +417,24 @@ class Checker:
         cv = Coverage()
         self._check(self.lib.rmc_get_coverage(self.ctx, C.byref(cv)))
         return {a: (cv.generated[k], cv.distinct[k]) for k, a in enumerate(COVERAGE_ACTIONS)}
+
+    def violations(self) -> Violations:
+        """rmc_get_violations after a run() on a ctx made with continue_=True (TLC
+        -continue): states, and per invariant r (bit 1 << r) first[r], each[r], depth[r]."""
+        v = Violations()
+        self._check(self.lib.rmc_get_violations(self.ctx, C.byref(v)))
+        return v
+
+    def trace_violation(self, bit):
+        """rmc_trace_violation: trace() to the least-index stored state that violates
+        the invariant `bit` (one INV_* bit of the config's mask) checked alone."""
+        n = C.c_size_t()
+        self._check(self.lib.rmc_trace_violation(self.ctx, bit, None, None, None, 0, C.byref(n)))
+        st = (StateView * n.value)()
+        fam = (C.c_int32 * n.value)()
+        inst = (C.c_int32 * n.value)()
+        self._check(self.lib.rmc_trace_violation(self.ctx, bit, st, fam, inst, n.value, C.byref(n)))
+        return [(fam[k], inst[k], st[k]) for k in range(n.value)]
 
     def result(self) -> Result:
         res = Result()

@@ -24,10 +24,11 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 12 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 13 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
                               rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys; 12: RMC_FLAG_CONTINUE,
-                              rmc_violations, rmc_get_violations, rmc_trace_violation */
+                              rmc_violations, rmc_get_violations, rmc_trace_violation; 13: RMC_FLAG_SYMMETRY on the wide
+                              layout (depth-bounded runs), rmc_state_keys on a wide ctx under it */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -39,8 +40,14 @@ extern "C" {
 #define RMC_MAX_DUP 3      /* per-message count bound <= 3 */
 /* Capacity of the wide encoding (DESIGN.md "Wide state"): a model with any
  * bound beyond the packed capacity — or a field no CONSTRAINT bounds, under a
- * depth bound or in simulation — runs on it (single GPU; no SYMMETRY;
- * RMC_FLAG_SPILL keeps its records in a ring window; RMC_FLAG_VERIFY_STATES
+ * depth bound or in simulation — runs on it (single GPU; RMC_FLAG_SYMMETRY
+ * keeps one state per orbit of Permutations(Server): the set holds canonical
+ * orbit keys, the records and traces are the states found, with the resident
+ * store and with the ring, for runs under a depth bound — max_depth > 0; a model
+ * whose CONSTRAINT exceeds the packed capacity searched to fixpoint under
+ * SYMMETRY is RMC_E_INVAL — with RMC_FLAG_VERIFY_STATES, RMC_FLAG_COVERAGE and
+ * RMC_FLAG_CONTINUE; RMC_FLAG_SPILL keeps its records in a ring window;
+ * RMC_FLAG_VERIFY_STATES
  * compares every fingerprint hit with the resident stored state, so the two
  * flags together are RMC_E_INVAL: at the depths that need the ring — depth 15
  * of MCraft.cfg as shipped, 2.24 G states, 2^33 set slots — the slot-to-state
@@ -69,7 +76,9 @@ extern "C" {
 #define RMC_E_IO (-61)         /* checkpoint file missing, unreadable or of another model */
 
 /* rmc_config.flags */
-#define RMC_FLAG_SYMMETRY (1u << 0)        /* SYMMETRY Permutations(Server)            */
+#define RMC_FLAG_SYMMETRY (1u << 0)        /* SYMMETRY Permutations(Server); both       */
+                                           /* layouts (rmc_shard: the packed one; the   */
+                                           /* wide one under max_depth > 0)             */
 #define RMC_FLAG_CHECK_DEADLOCK (1u << 1)  /* CHECK_DEADLOCK TRUE (TLC default)         */
 #define RMC_FLAG_BUG_QUORUM (1u << 2)      /* BecomeLeader guard raft.tla:197 weakened  */
                                            /* to votesGranted[i] /= {} (config 5)       */
@@ -78,7 +87,10 @@ extern "C" {
                                            /* differences = collisions (no TLC analog;  */
                                            /* single GPU).  Both layouts; on the wide   */
                                            /* one without RMC_FLAG_SPILL only (8 B more */
-                                           /* per set slot, every state resident)       */
+                                           /* per set slot, every state resident).      */
+                                           /* With RMC_FLAG_SYMMETRY the comparison is  */
+                                           /* "some permutation of the successor is the */
+                                           /* stored state" (both layouts)              */
 #define RMC_FLAG_SPILL (1u << 4)           /* frontier spill (TLC's states/ directory): */
                                            /* expanded levels leave the device window   */
                                            /* when it fills, so a model whose states    */
@@ -115,7 +127,8 @@ extern "C" {
 #define RMC_FLAG_COVERAGE (1u << 9)        /* action coverage (TLC -coverage): per-action  */
                                            /* generated / distinct counts of the BFS, read */
                                            /* with rmc_get_coverage.  Single GPU, both     */
-                                           /* layouts; no checkpoint / recover; ignored by */
+                                           /* layouts, with RMC_FLAG_SYMMETRY on both; no  */
+                                           /* checkpoint / recover; ignored by             */
                                            /* rmc_simulate                                 */
 /* (bit 10 is not assigned: rmc_create refuses it as an unknown flag bit) */
 #define RMC_FLAG_CONTINUE (1u << 11)       /* continue past violations (TLC -continue): a  */
@@ -123,7 +136,8 @@ extern "C" {
                                            /* violating states are stored and expanded, and */
                                            /* counted per invariant (rmc_get_violations).   */
                                            /* Single GPU; the wide layout without           */
-                                           /* RMC_FLAG_SPILL only; no checkpoint / recover; */
+                                           /* RMC_FLAG_SPILL only; with RMC_FLAG_SYMMETRY   */
+                                           /* on both layouts; no checkpoint / recover;     */
                                            /* ignored by rmc_simulate                       */
 
 /* rmc_config.invariants — the INVARIANT names the engine knows (fused checks).
@@ -201,6 +215,9 @@ typedef struct rmc_result {
     uint64_t collisions;       /* RMC_FLAG_VERIFY_STATES: fingerprint hits whose stored state */
                                /* differs (0 = the counts are exact, not probabilistic)   */
     uint64_t verified;         /* RMC_FLAG_VERIFY_STATES: hits compared state by state    */
+                               /* (wide layout: every probe is a new state or a compared  */
+                               /* hit, verified == probes - (distinct - 1); with           */
+                               /* RMC_FLAG_SYMMETRY too, orbit by orbit)                   */
     /* sharded mode (rmc_shard): this rank's exchange */
     uint64_t keys_sent;        /* phase-1 keys sent to other owners                        */
     uint64_t states_sent;      /* phase-2 accepted states shipped                          */
@@ -370,7 +387,8 @@ const char* rmc_coverage_action(int32_t row);
  * kernels are unchanged); without the flag nothing is allocated, launched or
  * read back for it.  Packed layout: resident, RMC_FLAG_SPILL (both windows),
  * SYMMETRY, RMC_FLAG_VERIFY_STATES, RMC_FLAG_COVERAGE.  Wide layout: resident
- * only — with RMC_FLAG_SPILL rmc_create is RMC_E_INVAL (the ring does not store
+ * only (SYMMETRY, RMC_FLAG_VERIFY_STATES and RMC_FLAG_COVERAGE included) — with
+ * RMC_FLAG_SPILL rmc_create is RMC_E_INVAL (the ring does not store
  * the last level of a max_depth run, so no pass can read it).  rmc_shard on a
  * ctx with the flag is RMC_E_INVAL, rmc_checkpoint and rmc_recover RMC_E_STATE
  * (the tallies are of whole runs and are not written). */
@@ -413,7 +431,9 @@ int rmc_recover(rmc_ctx* ctx, const char* path);
  * with RMC_FLAG_SPILL and max_depth the record of the last stored level).
  * rmc_expand: run the SAME device successor code as the BFS on n caller
  * states (no dedup) and return every enabled lane's successor.  *n_out
- * receives the number of successors even if it exceeds cap. */
+ * receives the number of successors even if it exceeds cap.  Under
+ * RMC_FLAG_SYMMETRY rmc_succ_view.fingerprint is the canonical key of the
+ * successor's orbit (both layouts), the state returned is the successor itself. */
 size_t rmc_state_bytes(const rmc_config* cfg);
 int rmc_expand(rmc_ctx* ctx, const rmc_state_view* states, size_t n, rmc_succ_view* out,
                size_t cap, size_t* n_out);
@@ -431,11 +451,13 @@ int rmc_check_states(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint3
                      int32_t* violated);
 /* Test hook: keys[t] = the 64-bit key (Fp.k) the search would insert for state t:
  * state_fp, under RMC_FLAG_SYMMETRY canon_state — the same device function k_seed,
- * k_rehash and k_publish call.  ref != NULL: same[t] = 1 iff verification's
- * comparison (same_state; under SYMMETRY same_orbit) finds state t equal to the
- * stored form of state ref[t] (ref[t] < n).  Packed layout only (the wide layout
- * has no SYMMETRY): RMC_E_INVAL on a wide ctx, for a view the encoder refuses, a
- * NULL array with n > 0, or ref[t] >= n; n = 0 launches nothing. */
+ * k_rehash and k_publish call; on a wide ctx under RMC_FLAG_SYMMETRY wcanon, as
+ * k_wseed and k_wexpand insert it.  ref != NULL: same[t] = 1 iff verification's
+ * comparison (same_state; under SYMMETRY same_orbit, on a wide ctx wsame_orbit)
+ * finds state t equal to the stored form of state ref[t] (ref[t] < n).
+ * RMC_E_INVAL on a wide ctx without RMC_FLAG_SYMMETRY (as before ABI 13), for a
+ * view the encoder refuses, a NULL array with n > 0, or ref[t] >= n; n = 0
+ * launches nothing. */
 int rmc_state_keys(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint64_t* keys,
                    const uint32_t* ref, uint8_t* same);
 

@@ -846,15 +846,10 @@ RMC_HD int uniform_draw(const u64 (&en)[NC], const u64 (&excl)[NC], u64& rs) {
 // k = sum of the components mod 2^64, s = sum of their smix (raft_packed.h Fp).
 // Unused log entries and message fields are 0 in the canonical form, so the
 // record's capacity does not enter.
+// (wcomp_srv_words / wcomp_msg_hdr: the mixing, given the words that name servers —
+// the SYMMETRY key calls them with those words mapped through a permutation)
 template <class St>
-RMC_HD u64 wcomp_srv(const St& s, int i, u64 salt) {
-    u64 w0 = (u64)s.ct[i] | ((u64)s.st[i] << 8) | ((u64)s.vf[i] << 16) | ((u64)s.ci[i] << 24) |
-             ((u64)s.len[i] << 32) | ((u64)s.vR[i] << 40) | ((u64)s.vG[i] << 48) | ((u64)i << 56);
-    u64 w1 = 0, w2 = 0;
-    for (int j = 0; j < WS; ++j) {
-        w1 |= (u64)s.ni[i][j] << (8 * j);
-        w2 |= (u64)s.mi[i][j] << (8 * j);
-    }
+RMC_HD u64 wcomp_srv_words(const St& s, int i, u64 w0, u64 w1, u64 w2, u64 salt) {
     u64 h = mix64(w0 ^ salt ^ 0x243F6A8885A308D3ull);
     h = mix64(h ^ w1 ^ (w2 << 40));
     h = mix64(h ^ (w2 >> 24));
@@ -867,10 +862,19 @@ RMC_HD u64 wcomp_srv(const St& s, int i, u64 salt) {
     }
     return h;
 }
+template <class St>
+RMC_HD u64 wcomp_srv(const St& s, int i, u64 salt) {
+    u64 w0 = (u64)s.ct[i] | ((u64)s.st[i] << 8) | ((u64)s.vf[i] << 16) | ((u64)s.ci[i] << 24) |
+             ((u64)s.len[i] << 32) | ((u64)s.vR[i] << 40) | ((u64)s.vG[i] << 48) | ((u64)i << 56);
+    u64 w1 = 0, w2 = 0;
+    for (int j = 0; j < WS; ++j) {
+        w1 |= (u64)s.ni[i][j] << (8 * j);
+        w2 |= (u64)s.mi[i][j] << (8 * j);
+    }
+    return wcomp_srv_words(s, i, w0, w1, w2, salt);
+}
 template <class Mg>
-RMC_HD u64 wcomp_msg(const Mg& m, int cnt, u64 salt) {
-    const u64 hdr = (u64)m.type | ((u64)m.term << 8) | ((u64)m.src << 16) | ((u64)m.dst << 24) |
-                    ((u64)(uint8_t)m.a << 32) | ((u64)m.b << 40) | ((u64)m.c << 48) | ((u64)m.n << 56);
+RMC_HD u64 wcomp_msg_hdr(const Mg& m, u64 hdr, int cnt, u64 salt) {
     u64 h = mix64(hdr ^ salt ^ 0x13198A2E03707344ull);
     h = mix64(h ^ (u64)(unsigned)cnt ^ 0xA4093822299F31D0ull);
     const int n = m.n;
@@ -881,6 +885,12 @@ RMC_HD u64 wcomp_msg(const Mg& m, int cnt, u64 salt) {
         h = mix64(h ^ lw ^ ((u64)e << 58));
     }
     return h;
+}
+template <class Mg>
+RMC_HD u64 wcomp_msg(const Mg& m, int cnt, u64 salt) {
+    const u64 hdr = (u64)m.type | ((u64)m.term << 8) | ((u64)m.src << 16) | ((u64)m.dst << 24) |
+                    ((u64)(uint8_t)m.a << 32) | ((u64)m.b << 40) | ((u64)m.c << 48) | ((u64)m.n << 56);
+    return wcomp_msg_hdr(m, hdr, cnt, salt);
 }
 template <class St>
 RMC_HD Fp wfp(const St& s, u64 salt, int S = WS) {
@@ -913,6 +923,251 @@ RMC_HD Fp wfp_delta(const St& s, const St& t, const Fp& h0, const WDelta& d, u64
         if (c > 1) fp_sub(h, wcomp_msg(t.msg[d.add_at], c - 1, salt));
     }
     return h;
+}
+
+// ---- SYMMETRY Permutations(Server) ---------------------------------------------------
+// Canonical key under SYMMETRY (the packed layout's contract, raft_packed.h
+// "Canonical key under SYMMETRY"): the least fingerprint (fp_less) of pi(s) over
+// the permutations pi that sort the servers by a permutation-invariant
+// signature, every order of tied servers included — the same set of states for
+// every member of the orbit, so the same key.  pi(s) is never materialised: wfp
+// is an order-free sum of one component per server and per message, so the
+// fingerprint of pi(s) comes straight from s's record — server i contributes as
+// index pi(i) with the ids it names mapped (votedFor, the bits of the vote
+// sets, the columns of nextIndex / matchIndex), a message with its source and
+// destination mapped, and the bag needs no re-sorting.  A permutation is packed
+// 3 bits per server (old id -> new id; pe of raft_packed.h).
+RMC_HD u32 wperm_id(u32 code, u32 x, int S) { return x < (u32)S ? pe(code, x) : x; }  // (Nil and ids no server has: kept)
+template <class St>
+RMC_HD u64 wcomp_srv_perm(const St& s, int i, u32 code, int S, u64 salt) {
+    const u32 keep = ~((1u << S) - 1u);
+    u32 vr = s.vR[i] & keep, vg = s.vG[i] & keep;
+    u64 w1 = 0, w2 = 0;
+    for (int j = 0; j < WS; ++j) {
+        const int pj = (int)wperm_id(code, (u32)j, S);
+        if (j < S) {
+            vr |= ((s.vR[i] >> j) & 1u) << pj;
+            vg |= ((s.vG[i] >> j) & 1u) << pj;
+        }
+        w1 |= (u64)s.ni[i][j] << (8 * pj);
+        w2 |= (u64)s.mi[i][j] << (8 * pj);
+    }
+    const u64 w0 = (u64)s.ct[i] | ((u64)s.st[i] << 8) | ((u64)wperm_id(code, s.vf[i], S) << 16) | ((u64)s.ci[i] << 24) |
+                   ((u64)s.len[i] << 32) | ((u64)vr << 40) | ((u64)vg << 48) | ((u64)pe(code, (u32)i) << 56);
+    return wcomp_srv_words(s, i, w0, w1, w2, salt);
+}
+template <class Mg>
+RMC_HD u64 wcomp_msg_perm(const Mg& m, int cnt, u32 code, int S, u64 salt) {
+    const u64 hdr = (u64)m.type | ((u64)m.term << 8) | ((u64)wperm_id(code, m.src, S) << 16) |
+                    ((u64)wperm_id(code, m.dst, S) << 24) | ((u64)(uint8_t)m.a << 32) | ((u64)m.b << 40) |
+                    ((u64)m.c << 48) | ((u64)m.n << 56);
+    return wcomp_msg_hdr(m, hdr, cnt, salt);
+}
+// wfp of pi(s) (the identity's is wfp(s)).
+template <class St>
+RMC_HD Fp wfp_perm(const St& s, u32 code, int S, u64 salt) {
+    Fp h{0, 0};
+    for (int i = 0; i < S; ++i) fp_add(h, wcomp_srv_perm(s, i, code, S, salt));
+    for (int q = 0; q < s.nmsg; ++q) fp_add(h, wcomp_msg_perm(s.msg[q], s.cnt[q], code, S, salt));
+    return h;
+}
+
+// Signature of server i, part 1 — what no permutation changes of its own
+// fields: term, role, commitIndex, the log, votedFor as Nil / self / other, the
+// sizes of the vote sets and whether they hold the server itself, its own
+// (nextIndex, matchIndex) and an order-free sum over its peers' pairs.  A lane
+// changes it for one server at most (WDelta.srv).
+template <class St>
+RMC_HD u64 wsig_base(const St& s, int i, int S) {
+    const u32 vf = s.vf[i], vr = s.vR[i], vg = s.vG[i];
+    const u64 w0 = (u64)s.ct[i] | ((u64)s.st[i] << 8) | ((u64)(vf == NIL ? 0u : vf == (u32)i ? 1u : 2u) << 16) |
+                   ((u64)s.ci[i] << 24) | ((u64)s.len[i] << 32) | ((u64)__builtin_popcount(vr) << 40) |
+                   ((u64)__builtin_popcount(vg) << 44) | ((u64)((vr >> i) & 1u) << 48) | ((u64)((vg >> i) & 1u) << 49);
+    u64 own = 0, peers = 0;
+    for (int j = 0; j < WS; ++j) {
+        if (j >= S) continue;
+        const u64 pr = (u64)s.ni[i][j] | ((u64)s.mi[i][j] << 8);
+        if (j == i) own = pr;
+        else peers += (pr + 1u) * (pr + 0x9E3779B1ull);
+    }
+    u64 h = mix64(w0 ^ 0x452821E638D01377ull);
+    h = mix64(h ^ own ^ (peers << 16));
+    const int n = s.len[i];
+    for (int e = 0; e < n; e += 4) {
+        u64 lw = 0;
+        for (int q = 0; q < 4 && e + q < n; ++q)
+            lw |= ((u64)s.log[i][e + q].term | ((u64)s.log[i][e + q].value << 8)) << (16 * q);
+        h = mix64(h ^ lw ^ ((u64)e << 58));
+    }
+    return h;
+}
+// Part 2: the messages the server sends and receives — type, term, body, the
+// number of entries and the count, the ids left out — summed order-free; the
+// signature is the two parts mixed.  sig[i] for i < S (the rest 0).
+struct WSig {
+    u64 v[WS];
+};
+template <class St>
+RMC_HD void wsignatures(const St& s, const u64 (&base)[WS], int S, WSig& sg) {
+    u64 ms[WS];
+    for (int i = 0; i < WS; ++i) ms[i] = 0;
+    for (int q = 0; q < s.nmsg; ++q) {
+        const typename St::Msg& m = s.msg[q];
+        u64 x = (u64)m.type | ((u64)m.term << 8) | ((u64)s.cnt[q] << 16) | ((u64)(uint8_t)m.a << 32) | ((u64)m.b << 40) |
+                ((u64)m.c << 48) | ((u64)m.n << 56);
+        x *= 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 29)) * 0xBF58476D1CE4E5B9ull;
+        const u64 a = x ^ (x >> 32), b = (a * 0x94D049BB133111EBull) + 0x7F4A7C15ull;
+        for (int i = 0; i < WS; ++i) ms[i] += (m.src == i ? a : 0ull) + (m.dst == i ? b : 0ull);
+    }
+    for (int i = 0; i < WS; ++i) sg.v[i] = i < S ? mix64(base[i] ^ ms[i]) : 0ull;
+}
+// Rank of every server by signature (3 bits each in *lo: server i -> its rank,
+// the sorting permutation when nothing ties), the size of its tie class in *tc,
+// and whether any two servers tie (raft_packed.h sig_rank).
+RMC_HD bool wsig_rank(const WSig& sg, int S, u32* lo, u32* tc) {
+    u32 l = 0, c = 0;
+    bool tie = false;
+    for (int i = 0; i < WS; ++i) {
+        if (i >= S) continue;
+        u32 r = 0, n = 0;
+        for (int j = 0; j < WS; ++j) {
+            if (j >= S) continue;
+            r += sg.v[j] < sg.v[i] ? 1u : 0u;
+            n += sg.v[j] == sg.v[i] ? 1u : 0u;
+        }
+        l |= r << (3 * i);
+        c |= n << (3 * i);
+        tie |= n > 1;
+    }
+    *lo = l;
+    *tc = c;
+    return tie;
+}
+// The p-th of the S! permutations of 0..S-1 (factorial number system), packed.
+RMC_HD int wperm_count(int S) {
+    int n = 1;
+    for (int i = 2; i <= S; ++i) n *= i;
+    return n;
+}
+RMC_HD u32 wperm_code(int p, int S) {
+    u32 code = 0, used = 0;
+    for (int i = 0; i < S; ++i) {
+        const int r = S - i;
+        int d = p % r;
+        p /= r;
+        u32 pos = 0;
+        for (int x = 0; x < S; ++x) {  // the d-th position not taken yet
+            if ((used >> x) & 1u) continue;
+            if (d-- == 0) {
+                pos = (u32)x;
+                break;
+            }
+        }
+        used |= 1u << pos;
+        code |= pos << (3 * i);
+    }
+    return code;
+}
+// Ties (rare; out of line on the device): the least fingerprint over every order
+// of the tied servers, i.e. over the permutations that put server i at a
+// position in [lo_i, lo_i + tc_i).
+template <class St>
+RMC_HD_COLD Fp wcanon_ties(const St& s, u32 lo, u32 tc, int S, u64 salt) {
+    Fp best{~0ull, ~0u};
+    const int np = wperm_count(S);
+    for (int p = 0; p < np; ++p) {
+        const u32 c = wperm_code(p, S);
+        bool ok = true;
+        for (int i = 0; i < S; ++i) {
+            const u32 pos = pe(c, (u32)i), l = pe(lo, (u32)i);
+            ok &= pos >= l && pos < l + pe(tc, (u32)i);
+        }
+        if (!ok) continue;
+        const Fp h = wfp_perm(s, c, S, salt);
+        best = fp_less(h, best) ? h : best;
+    }
+    return best;
+}
+// The canonical key of a record from its servers' signature bases.
+template <class St>
+RMC_HD Fp wcanon_based(const St& s, const u64 (&base)[WS], int S, u64 salt) {
+    WSig sg;
+    wsignatures(s, base, S, sg);
+    u32 lo, tc;
+    if (!wsig_rank(sg, S, &lo, &tc)) return wfp_perm(s, lo, S, salt);  // the sorting permutation
+    return wcanon_ties(s, lo, tc, S, salt);
+}
+template <class St>
+RMC_HD void wsig_bases(const St& s, int S, u64 (&base)[WS]) {
+    for (int i = 0; i < WS; ++i) base[i] = i < S ? wsig_base(s, i, S) : 0ull;
+}
+template <class St>
+RMC_HD Fp wcanon(const St& s, u64 salt, int S = WS) {
+    u64 base[WS];
+    wsig_bases(s, S, base);
+    return wcanon_based(s, base, S, salt);
+}
+// The canonical key of the successor t a lane made of a state with signature
+// bases base0: only the server the lane may have written (WDelta.srv) has another.
+template <class St>
+RMC_HD Fp wcanon_succ(const St& t, const u64 (&base0)[WS], int srv, u64 salt, int S) {
+    u64 base[WS];
+    for (int i = 0; i < WS; ++i) base[i] = i == srv ? wsig_base(t, i, S) : base0[i];
+    return wcanon_based(t, base, S, salt);
+}
+
+// Orbit equality of two canonical records of any two types (RMC_FLAG_VERIFY_STATES
+// under SYMMETRY; the packed twin is same_orbit): some permutation of a is b.
+// wsame_perm compares pi(a) with b in place — server i of a with server pi(i)
+// of b, the ids it names mapped, and every message of a, its servers mapped,
+// looked up in b's bag with its count (the bags have equally many distinct
+// messages and pi is one-to-one, so that is bag equality).  Lengths are checked
+// before entries are read, as in wsame.
+template <class A, class B>
+RMC_HD bool wsame_perm(const A& a, const B& b, u32 code, int S) {
+    constexpr int L = A::kLW < B::kLW ? A::kLW : B::kLW, K = A::kKW < B::kKW ? A::kKW : B::kKW;
+    if (a.nmsg != b.nmsg || a.nmsg > K) return false;
+    for (int i = 0; i < S; ++i) {
+        const int pi = (int)pe(code, (u32)i);
+        if (a.ct[i] != b.ct[pi] || a.st[i] != b.st[pi] || a.ci[i] != b.ci[pi] || a.len[i] != b.len[pi] ||
+            wperm_id(code, a.vf[i], S) != b.vf[pi])
+            return false;
+        for (int j = 0; j < S; ++j) {
+            const int pj = (int)pe(code, (u32)j);
+            if (((a.vR[i] >> j) & 1u) != ((b.vR[pi] >> pj) & 1u) || ((a.vG[i] >> j) & 1u) != ((b.vG[pi] >> pj) & 1u) ||
+                a.ni[i][j] != b.ni[pi][pj] || a.mi[i][j] != b.mi[pi][pj])
+                return false;
+        }
+        if (a.len[i] > L) return false;
+        for (int x = 0; x < a.len[i]; ++x)
+            if (a.log[i][x].term != b.log[pi][x].term || a.log[i][x].value != b.log[pi][x].value) return false;
+    }
+    for (int q = 0; q < a.nmsg; ++q) {
+        const typename A::Msg& m = a.msg[q];
+        if (m.n > L) return false;
+        const u32 src = wperm_id(code, m.src, S), dst = wperm_id(code, m.dst, S);
+        bool found = false;
+        for (int r = 0; r < b.nmsg && !found; ++r) {
+            const typename B::Msg& o = b.msg[r];
+            if (a.cnt[q] != b.cnt[r] || m.type != o.type || m.term != o.term || src != o.src || dst != o.dst ||
+                m.a != o.a || m.b != o.b || m.c != o.c || m.n != o.n)
+                continue;
+            found = true;
+            for (int x = 0; x < m.n; ++x)
+                if (m.e[x].term != o.e[x].term || m.e[x].value != o.e[x].value) found = false;
+        }
+        if (!found) return false;
+    }
+    return true;
+}
+template <class A, class B>
+RMC_HD_COLD bool wsame_orbit(const A& a, const B& b, int S = WS) {
+    if (a.nmsg != b.nmsg) return false;
+    const int np = wperm_count(S);
+    for (int p = 0; p < np; ++p)
+        if (wsame_perm(a, b, wperm_code(p, S), S)) return true;
+    return false;
 }
 
 }  // namespace wide

@@ -988,13 +988,17 @@ int rmc_check_states(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_
 int rmc_state_keys(rmc_ctx* c, const rmc_state_view* states, size_t n, uint64_t* keys, const uint32_t* ref,
                    uint8_t* same) {
     if (!c) return RMC_E_INVAL;
-    if (c->wide) return fail(c, RMC_E_INVAL, "rmc_state_keys: the packed layout only");
+    // a wide ctx: under SYMMETRY (the canonical keys this hook exists for); without it the
+    // refusal of ABI 11 stands
+    if (c->wide && !c->WB.sym)
+        return fail(c, RMC_E_INVAL, "rmc_state_keys: the packed layout only, or a wide ctx under RMC_FLAG_SYMMETRY");
     if (n && (!states || !keys || (ref && !same)))
         return fail(c, RMC_E_INVAL, "rmc_state_keys: states, keys or same is NULL");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (n == 0) return 0;
     for (size_t t = 0; ref && t < n; ++t)
         if (ref[t] >= n) return fail(c, RMC_E_INVAL, "rmc_state_keys: ref[" + std::to_string(t) + "] is not below n");
+    if (c->wide) return keys_wide(c, states, n, keys, ref, same);
     const int NW = c->NW;
     std::vector<u32> packed(n * (size_t)NW);
     std::string why;

@@ -272,6 +272,7 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user);
 int trace_wide(rmc_ctx* c, rmc::u64 target, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
                size_t* len);
 int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_view* out, size_t cap, size_t* n_out);
+int keys_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint64_t* keys, const uint32_t* ref, uint8_t* same);
 int check_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t mask, int32_t* violated);
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, rmc::i64 rec_beh,
              std::vector<rmc_state_view>* rec);

@@ -234,6 +234,8 @@ struct WideBufs {
     u64 vcap;         // records in vbuf
     u64 vbase;        // per launch: Counters.count when it began (owners at or above it are deferred)
     u64 fp_mask;      // fingerprint bits kept (~0 = all; rmc_set_fp_bits)
+    int sym;          // RMC_FLAG_SYMMETRY: the set holds canonical orbit keys (wcanon), verification
+                      // compares orbits (wsame_orbit); the records stored are the states found
 };
 // One successor listed by k_wlist (rmc_expand on the wide layout).
 struct WSucc {
@@ -251,7 +253,12 @@ hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64
 // ShapeKernels::violations on the wide records (k_wviolations; the resident store only)
 hipError_t launch_wviolations(const WModel& M, const WideBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
                               hipStream_t st);
+// sym: WSucc.fp is the canonical key under SYMMETRY (wcanon), else wfp
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
+                        u64 salt, int sym, hipStream_t st);
+// rmc_state_keys on a wide ctx under SYMMETRY (k_wkeys): keys[t] as the search inserts it (wcanon),
+// same[t] (ref given) by its verification's comparison of in[t] with in[ref[t]] (wsame_orbit)
+hipError_t launch_wkeys(const WModel& M, const WState* in, u64 n, u64* keys, const u32* ref, unsigned char* same,
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,
                             SimCounters* out, i64 rec_beh, WState* rec, hipStream_t st);

@@ -194,7 +194,8 @@ int usage() {
             "  -nospill   keep every state on the device (stop with a capacity error when it fills);\n"
             "             by default expanded levels leave the device window (single GPU; their trace\n"
             "             links stay in HBM, or move to pinned host memory).  Runs on the wide layout\n"
-            "             (-depth runs of models with unbounded fields) spill too, unless -verify\n"
+            "             (-depth runs of models with unbounded fields, SYMMETRY Permutations(Server)\n"
+            "             included) spill too, unless -verify\n"
             "  -window N  states kept on the device when spilling (default: what the set leaves;\n"
             "             the wide layout keeps exactly N records, the packed one rounds up to 2^k)\n"
             "  -fpseed S  fingerprint salt (TLC -fp: another member of the fingerprint family)\n"

@@ -37,8 +37,14 @@ int validate_wide(const rmc_config* c, std::string* why) {
     if (c->max_log_len < 0 || c->max_log_len > RMC_WIDE_MAX_LOG) return bad("max_log_len must be 0..32 (wide layout)");
     if (c->max_msgs < 0 || c->max_msgs > RMC_WIDE_MAX_MSGS) return bad("max_msgs must be 0..64 (wide layout)");
     if (c->max_dup < 1 || c->max_dup > RMC_WIDE_MAX_DUP) return bad("max_dup must be 1..255 (wide layout)");
-    if (c->flags & RMC_FLAG_SYMMETRY)
-        return bad("the wide layout (bounds beyond the packed capacity) supports no SYMMETRY");
+    // SYMMETRY on this layout: runs under a depth bound (the reference's MCraft.cfg as
+    // shipped under -depth, what it was built for) and RMC_FORCE_WIDE runs; a model whose
+    // CONSTRAINT exceeds the packed capacity searched to fixpoint stays refused, as before
+    if ((c->flags & RMC_FLAG_SYMMETRY) && c->max_depth <= 0 &&
+        (c->max_term > RMC_MAX_TERM || c->max_log_len > RMC_MAX_LOG || c->max_msgs > RMC_MAX_MSGS ||
+         c->max_dup > RMC_MAX_DUP))
+        return bad("the wide layout (bounds beyond the packed capacity) supports SYMMETRY only under a depth "
+                   "bound (max_depth > 0)");
     // verification compares a hit with its owner's resident record, found through 8 B
     // more per set slot; at the depths that need the ring that array no longer fits
     // beside the set and the window (DESIGN.md "Wide state")
@@ -170,6 +176,7 @@ int create_wide(rmc_ctx* c) {
     B.verify = verify ? 1 : 0;
     B.vcap = in.vcap;
     B.fp_mask = ~0ull;
+    B.sym = (c->cfg.flags & RMC_FLAG_SYMMETRY) ? 1 : 0;
     if (hipMalloc(&B.store, win * rec) != hipSuccess || hipMalloc(&B.parent, cap * 8) != hipSuccess ||
         hipMalloc(&B.act, cap) != hipSuccess || hipMalloc(&B.table, slots * 8) != hipSuccess ||
         hipMalloc(&B.ctr, sizeof(Counters)) != hipSuccess || hipMalloc(&c->w_staged, sizeof(WState)) != hipSuccess ||
@@ -390,7 +397,8 @@ int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_vie
     HIPCHK(c, d_cnt.alloc(1));
     HIPCHK(c, hipMemcpy(d_in.get(), in.data(), n * sizeof(WState), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(d_cnt.get(), 0, 8));
-    HIPCHK(c, launch_wlist(c->WM, d_in.get(), (u64)n, d_out.get(), rcap, d_cnt.get(), wide_salt(c->cfg.seed), c->st));
+    HIPCHK(c, launch_wlist(c->WM, d_in.get(), (u64)n, d_out.get(), rcap, d_cnt.get(), wide_salt(c->cfg.seed),
+                           c->WB.sym, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     unsigned long long cnt = 0;
     HIPCHK(c, hipMemcpy(&cnt, d_cnt.get(), 8, hipMemcpyDeviceToHost));
@@ -411,6 +419,33 @@ int expand_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, rmc_succ_vie
         if (s.in_constraint) decode_wide(c->WM.S, recs[q].state, &s.state);
     }
     *n_out = (size_t)cnt;
+    return 0;
+}
+
+// rmc_state_keys on a wide ctx under SYMMETRY: the views as full records through k_wkeys.
+int keys_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint64_t* keys, const uint32_t* ref, uint8_t* same) {
+    std::vector<WState> in(n);
+    std::string why;
+    for (size_t t = 0; t < n; ++t)
+        if (encode_wide(c->WM.S, states[t], &in[t], &why))
+            return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
+    DevScratch<WState> d_in;
+    DevScratch<u32> d_ref;
+    DevScratch<u64> d_keys;
+    DevScratch<unsigned char> d_same;
+    HIPCHK(c, d_in.alloc(n));
+    HIPCHK(c, d_keys.alloc(n));
+    HIPCHK(c, hipMemcpy(d_in.get(), in.data(), n * sizeof(WState), hipMemcpyHostToDevice));
+    if (ref) {
+        HIPCHK(c, d_ref.alloc(n));
+        HIPCHK(c, d_same.alloc(n));
+        HIPCHK(c, hipMemcpy(d_ref.get(), ref, n * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, launch_wkeys(c->WM, d_in.get(), (u64)n, d_keys.get(), ref ? d_ref.get() : nullptr,
+                           ref ? d_same.get() : nullptr, wide_salt(c->cfg.seed), c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(keys, d_keys.get(), n * 8, hipMemcpyDeviceToHost));
+    if (ref) HIPCHK(c, hipMemcpy(same, d_same.get(), n, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -80,13 +80,16 @@ __device__ __forceinline__ u32 w_store(const WModel& M, const WideBufs& B, u64 n
 
 // Init (raft.tla:125-129) or SmokeInit's states: n staged records (of the work type).
 // Verify (RMC_FLAG_VERIFY_STATES): the key is weakened as the expansion's and
-// the new state becomes its slot's owner.
-template <class Store, class Work, bool Ring, bool Verify>
+// the new state becomes its slot's owner.  Sym (RMC_FLAG_SYMMETRY): the key is the
+// canonical key of the state's orbit (wcanon); the record stored is the state given.
+template <class Store, class Work, bool Ring, bool Verify, bool Sym>
 __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B, const Work* staged, u64 n) {
     static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
     static_assert(!(Ring && Verify), "verification compares with resident records");
     for (u64 t = (u64)blockIdx.x * 256ull + threadIdx.x; t < n; t += (u64)gridDim.x * 256ull) {
-        Fp h = wfp(staged[t], B.salt, M.S);
+        Fp h;
+        if constexpr (Sym) h = wcanon(staged[t], B.salt, M.S);
+        else h = wfp(staged[t], B.salt, M.S);
         if constexpr (Verify) h = fp_weaken(h, B.fp_mask);
         u64 slot;
         if (!w_insert(B.table, B.tmask, h, &B.ctr->table_full, &slot)) continue;
@@ -124,7 +127,15 @@ __global__ __launch_bounds__(256) void k_wseed(const WModel M, const WideBufs B,
 // (rmc_set_fp_bits), and the stutter shortcut — taken on the full fingerprint —
 // is confirmed on the states, so every probe is either a new state or a
 // compared hit: verified = probes - (distinct - 1).
-template <class Store, class Work, bool Ring, bool Verify>
+// Sym (RMC_FLAG_SYMMETRY): the key of a successor is its orbit's canonical key,
+// computed on the materialised successor t from the parent's signature bases
+// (wcanon_succ: the one server the lane wrote gets a new base) — no permuted
+// record, no third Work.  The record stored is the successor found.  The
+// stutter shortcut compares canonical keys: a successor in its parent's orbit
+// is already stored; with Verify that is confirmed by wsame_orbit, and both
+// compare sites decide "some permutation of the successor is the owner".  The
+// non-symmetric instantiations are what they were.
+template <class Store, class Work, bool Ring, bool Verify, bool Sym>
 __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs B, u64 lo, u64 hi) {
     static_assert(Ring || sizeof(Store) == sizeof(Work), "without the ring the store holds the work record");
     static_assert(Store::kLW <= Work::kLW && Store::kKW <= Work::kKW, "the work record holds every stored state");
@@ -135,7 +146,14 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
     for (u64 i = lo + (u64)blockIdx.x * 256ull + threadIdx.x; i < hi; i += (u64)gridDim.x * 256ull) {
         Work s, t;
         wconvert(s, static_cast<const Store*>(B.store)[w_slot<Ring>(B, i)]);
-        const Fp h0 = wfp(s, B.salt, M.S);
+        Fp h0;
+        u64 base0[Sym ? WS : 1];
+        if constexpr (Sym) {
+            wsig_bases(s, M.S, base0);
+            h0 = wcanon_based(s, base0, M.S, B.salt);
+        } else {
+            h0 = wfp(s, B.salt, M.S);
+        }
         u32 g = 0;
         // lanes of families 0-6, then the three bag families over slots [0, nmsg)
         const int nb = s.nmsg, nl = o7 + 3 * nb;
@@ -150,9 +168,15 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
                 continue;
             }
             if (!win_model(M, t)) continue;
-            const Fp h = wfp_delta(s, t, h0, dl, B.salt);
-            // a stutter (without Verify: or a full-fingerprint twin of the parent)
-            if (h.k == h0.k && h.s == h0.s && (!Verify || wsame(s, t, M.S))) continue;
+            Fp h;
+            if constexpr (Sym) h = wcanon_succ(t, base0, dl.srv, B.salt, M.S);
+            else h = wfp_delta(s, t, h0, dl, B.salt);
+            // a stutter (without Verify: or a full-fingerprint twin of the parent); Sym: in the parent's orbit
+            if constexpr (Sym) {
+                if (h.k == h0.k && h.s == h0.s && (!Verify || wsame_orbit(s, t, M.S))) continue;
+            } else {
+                if (h.k == h0.k && h.s == h0.s && (!Verify || wsame(s, t, M.S))) continue;
+            }
             ++probes;
             u64 slot;
             if (!w_insert(B.table, B.tmask, Verify ? fp_weaken(h, B.fp_mask) : h, &B.ctr->table_full, &slot)) {
@@ -161,7 +185,8 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
                     const u64 ix = B.sidx[slot];
                     if (ix != ~0ull && ix < B.vbase) {
                         ++vchk;
-                        vcol += wsame(static_cast<const Store*>(B.store)[ix], t, M.S) ? 0u : 1u;
+                        if constexpr (Sym) vcol += wsame_orbit(static_cast<const Store*>(B.store)[ix], t, M.S) ? 0u : 1u;
+                        else vcol += wsame(static_cast<const Store*>(B.store)[ix], t, M.S) ? 0u : 1u;
                         continue;
                     }
                     // the owner is of this launch: deferred, one vcount bump for the lanes here together
@@ -208,7 +233,7 @@ __global__ __launch_bounds__(256) void k_wexpand(const WModel M, const WideBufs 
 // successor is re-derived from its parent's record by its lane and compared
 // with the owner's.  A hit without an owner (or a record out of range) is
 // Counters.overflow bit 3, an internal error.
-template <class St>
+template <class St, bool Sym>
 __global__ __launch_bounds__(256) void k_wverify(const WModel M, const WideBufs B, u64 n) {
     u64 vchk = 0, vcol = 0;
     const St* store = static_cast<const St*>(B.store);
@@ -223,7 +248,8 @@ __global__ __launch_bounds__(256) void k_wverify(const WModel M, const WideBufs 
             continue;
         }
         ++vchk;
-        vcol += wsame(store[ix], t, M.S) ? 0u : 1u;
+        if constexpr (Sym) vcol += wsame_orbit(store[ix], t, M.S) ? 0u : 1u;
+        else vcol += wsame(store[ix], t, M.S) ? 0u : 1u;
     }
     vchk = w_wave_sum(vchk);
     vcol = w_wave_sum(vcol);
@@ -369,7 +395,9 @@ __global__ __launch_bounds__(256) void k_wviolations(const WModel M, const WideB
     }
 }
 
-// Every enabled lane of n given states, without dedup (rmc_expand).
+// Every enabled lane of n given states, without dedup (rmc_expand).  Sym: the
+// fingerprint listed is the successor's canonical key, as k_wexpand would insert it.
+template <bool Sym>
 __global__ __launch_bounds__(64) void k_wlist(const WModel M, const WState* in, u64 n, WSucc* out, u64 cap,
                                              unsigned long long* count, u64 salt) {
     const u64 p = (u64)blockIdx.x * 64ull + threadIdx.x;
@@ -386,12 +414,22 @@ __global__ __launch_bounds__(64) void k_wlist(const WModel M, const WState* in, 
         w.code = r;
         const int inm = r == W_ON && win_model(M, t);
         w.in_model = inm;
-        w.fp = inm ? wfp(t, salt, M.S).k : 0ull;
+        w.fp = !inm ? 0ull : Sym ? wcanon(t, salt, M.S).k : wfp(t, salt, M.S).k;
         if (inm) wcopy_state(w.state, t);
         else wzero(&w.state, (int)sizeof(WState));
     }
 }
-
+// The keys of n given states under SYMMETRY, one thread per state (rmc_state_keys on
+// a wide ctx; the packed twin is k_keys): the key k_wseed and k_wexpand insert for
+// the state (wcanon), and with ref whether their verification's comparison
+// (wsame_orbit) finds state t equal to state ref[t].
+__global__ __launch_bounds__(64) void k_wkeys(const WModel M, const WState* in, u64 n, u64* keys, const u32* ref,
+                                             unsigned char* same, u64 salt) {
+    const u64 p = (u64)blockIdx.x * 64ull + threadIdx.x;
+    if (p >= n) return;
+    keys[p] = wcanon(in[p], salt, M.S).k;
+    if (ref) same[p] = wsame_orbit(in[p], in[ref[p]], M.S) ? 1 : 0;  // (ref[p] < n: checked by the host)
+}
 
 // ---- one wave on one record in LDS (k_wsimulate_w) ----------------------------------
 // Every lane of the wave calls these with the same arguments; lane q handles
@@ -738,6 +776,13 @@ static bool w_dispatch(const WideBufs& B, F f) {
     return false;  // a work record smaller than the store's: no such kernel
 }
 
+// B.sym (RMC_FLAG_SYMMETRY): the instantiation with the canonical key.
+template <class F>
+static void w_sym(const WideBufs& B, F f) {
+    if (B.sym) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // (B.verify: the Verify kernels, which exist for the resident store only)
 hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, u64 n, hipStream_t st) {
     if (!n) return hipSuccess;
@@ -747,15 +792,18 @@ hipError_t launch_wseed(const WModel& M, const WideBufs& B, const void* staged, 
         typedef std::remove_pointer_t<decltype(wp)> Work;
         constexpr bool Ring = decltype(ring)::value;
         const dim3 grid(grid_for(n, 256, 1024));
-        if constexpr (!Ring) {
-            if (B.verify) {
-                hipLaunchKernelGGL((k_wseed<Store, Work, false, true>), grid, dim3(256), 0, st, M, B,
-                                   static_cast<const Work*>(staged), n);
-                return;
+        w_sym(B, [&](auto sym) {
+            constexpr bool Sym = decltype(sym)::value;
+            if constexpr (!Ring) {
+                if (B.verify) {
+                    hipLaunchKernelGGL((k_wseed<Store, Work, false, true, Sym>), grid, dim3(256), 0, st, M, B,
+                                       static_cast<const Work*>(staged), n);
+                    return;
+                }
             }
-        }
-        hipLaunchKernelGGL((k_wseed<Store, Work, Ring, false>), grid, dim3(256), 0, st, M, B,
-                           static_cast<const Work*>(staged), n);
+            hipLaunchKernelGGL((k_wseed<Store, Work, Ring, false, Sym>), grid, dim3(256), 0, st, M, B,
+                               static_cast<const Work*>(staged), n);
+        });
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -767,13 +815,16 @@ hipError_t launch_wexpand(const WModel& M, const WideBufs& B, u64 lo, u64 hi, hi
         typedef std::remove_pointer_t<decltype(wp)> Work;
         constexpr bool Ring = decltype(ring)::value;
         const dim3 grid(grid_for(hi - lo, 256, 4096));
-        if constexpr (!Ring) {
-            if (B.verify) {
-                hipLaunchKernelGGL((k_wexpand<Store, Work, false, true>), grid, dim3(256), 0, st, M, B, lo, hi);
-                return;
+        w_sym(B, [&](auto sym) {
+            constexpr bool Sym = decltype(sym)::value;
+            if constexpr (!Ring) {
+                if (B.verify) {
+                    hipLaunchKernelGGL((k_wexpand<Store, Work, false, true, Sym>), grid, dim3(256), 0, st, M, B, lo, hi);
+                    return;
+                }
             }
-        }
-        hipLaunchKernelGGL((k_wexpand<Store, Work, Ring, false>), grid, dim3(256), 0, st, M, B, lo, hi);
+            hipLaunchKernelGGL((k_wexpand<Store, Work, Ring, false, Sym>), grid, dim3(256), 0, st, M, B, lo, hi);
+        });
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -781,9 +832,12 @@ hipError_t launch_wverify(const WModel& M, const WideBufs& B, u64 n, hipStream_t
     if (!n) return hipSuccess;
     if (!B.verify || B.window || n > B.vcap) return hipErrorInvalidValue;
     const dim3 grid(grid_for(n, 256, 4096));
-    if (B.compact == 2) hipLaunchKernelGGL(k_wverify<WStateD>, grid, dim3(256), 0, st, M, B, n);
-    else if (B.compact) hipLaunchKernelGGL(k_wverify<WStateC>, grid, dim3(256), 0, st, M, B, n);
-    else hipLaunchKernelGGL(k_wverify<WState>, grid, dim3(256), 0, st, M, B, n);
+    w_sym(B, [&](auto sym) {
+        constexpr bool Sym = decltype(sym)::value;
+        if (B.compact == 2) hipLaunchKernelGGL((k_wverify<WStateD, Sym>), grid, dim3(256), 0, st, M, B, n);
+        else if (B.compact) hipLaunchKernelGGL((k_wverify<WStateC, Sym>), grid, dim3(256), 0, st, M, B, n);
+        else hipLaunchKernelGGL((k_wverify<WState, Sym>), grid, dim3(256), 0, st, M, B, n);
+    });
     return hipGetLastError();
 }
 hipError_t launch_wcover(const WModel& M, const WideBufs& B, u64 lo, u64 hi, u64 nlo, u64 nhi, u64 n_init,
@@ -809,9 +863,17 @@ hipError_t launch_wviolations(const WModel& M, const WideBufs& B, u64 nlo, u64 n
     return hipGetLastError();
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,
+                        u64 salt, int sym, hipStream_t st) {
+    if (!n) return hipSuccess;
+    const dim3 grid(grid_for(n, 64, 1u << 20));
+    if (sym) hipLaunchKernelGGL(k_wlist<true>, grid, dim3(64), 0, st, M, in, n, out, cap, count, salt);
+    else hipLaunchKernelGGL(k_wlist<false>, grid, dim3(64), 0, st, M, in, n, out, cap, count, salt);
+    return hipGetLastError();
+}
+hipError_t launch_wkeys(const WModel& M, const WState* in, u64 n, u64* keys, const u32* ref, unsigned char* same,
                         u64 salt, hipStream_t st) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_wlist, dim3(grid_for(n, 64, 1u << 20)), dim3(64), 0, st, M, in, n, out, cap, count, salt);
+    hipLaunchKernelGGL(k_wkeys, dim3(grid_for(n, 64, 1u << 20)), dim3(64), 0, st, M, in, n, keys, ref, same, salt);
     return hipGetLastError();
 }
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,

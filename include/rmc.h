@@ -24,11 +24,12 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 13 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 14 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
                               rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys; 12: RMC_FLAG_CONTINUE,
                               rmc_violations, rmc_get_violations, rmc_trace_violation; 13: RMC_FLAG_SYMMETRY on the wide
-                              layout (depth-bounded runs), rmc_state_keys on a wide ctx under it */
+                              layout (depth-bounded runs), rmc_state_keys on a wide ctx under it; 14: the state
+                              graph: rmc_get_levels, rmc_read_states, rmc_find_states, rmc_graph_edges */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -460,6 +461,63 @@ int rmc_check_states(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint3
  * launches nothing. */
 int rmc_state_keys(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint64_t* keys,
                    const uint32_t* ref, uint8_t* same);
+
+/* ---- state graph export (TLC -dump FILE, -dump dot,actionlabels FILE) -----------
+ * After a completed rmc_run_bfs the ctx holds the whole state graph in HBM: the
+ * stored states in level order, and the fingerprint set that tells which stored
+ * state a successor is.  These calls read it.  Packed layout, single GPU,
+ * resident store; with RMC_FLAG_SYMMETRY (the nodes are the stored orbit
+ * representatives), RMC_FLAG_VERIFY_STATES, RMC_FLAG_COVERAGE, RMC_FLAG_CONTINUE.
+ *
+ * rmc_get_levels (both layouts): starts[l] = the store index of the first state
+ * of level l + 1, the last entry = rmc_result.distinct; *n receives the number
+ * of entries (depth + 1) even if it exceeds cap.
+ * rmc_read_states: the stored states [first, first + n) decoded, and (keys !=
+ * NULL) the 64-bit key the search inserted for each: rmc_state_keys' notion,
+ * state_fp, canon_state under RMC_FLAG_SYMMETRY.
+ * rmc_find_states: index[t] = the store index of the stored state that holds
+ * caller state t's key, or RMC_NO_STATE.  Under RMC_FLAG_SYMMETRY any member of
+ * an orbit finds the stored representative.
+ * rmc_graph_edges: every edge out of the stored states [lo, hi).
+ *  - A source has edges only if the run expanded it: the indices below
+ *    distinct - left_on_queue.  The states of an unexpanded last level (max_depth,
+ *    a callback stop) have none, as in TLC's dump of a stopped run.
+ *  - An expanded source yields one edge per enabled lane whose successor
+ *    satisfies the CONSTRAINT; stuttering lanes included (dst = the source
+ *    itself; under SYMMETRY the stored representative of its orbit, which is the
+ *    source); two lanes that reach the same state give two edges.
+ *  - family and instance are rmc_succ_view's.
+ *  - dst = the index of the stored state that holds the successor's key, looked
+ *    up exactly as the search computes it (rmc_set_fp_bits, the salt of
+ *    rmc_config.seed and the set's epoch tag all apply; under SYMMETRY the
+ *    canonical key).  An edge whose key the set does not hold is an engine
+ *    error: RMC_E_HIP naming the source index and the lane, never dropped.
+ *  - Order: ascending src, then ascending instance, the same at every call.
+ *  - *n_out receives the number of edges even if it exceeds cap; a range of any
+ *    size is served in internal chunks; lo == hi launches nothing.
+ * The lookup is a slot -> store index array of 8 B per fingerprint-set slot: a
+ * ctx with RMC_FLAG_VERIFY_STATES has it; any other ctx allocates it at its first
+ * rmc_find_states / rmc_graph_edges (RMC_E_NOMEM if it does not fit beside the
+ * store and the set: give rmc_config.state_capacity or set_bytes) and fills it
+ * with one pass over the stored states; rmc_destroy frees it; the next
+ * rmc_run_bfs invalidates it.
+ * Refusals (each with a message): a NULL ctx, or a NULL array with n > 0 (cap >
+ * 0), is RMC_E_INVAL; a range beyond rmc_result.distinct and a view the encoder
+ * refuses are RMC_E_INVAL; RMC_E_STATE: before a completed rmc_run_bfs; after
+ * rmc_recover and before the next run; on a sharded ctx (rmc_shard); on a ctx
+ * created with RMC_FLAG_SPILL (the states must be resident); on a wide ctx, for
+ * all but rmc_get_levels; and rmc_graph_edges after a run that stopped at a
+ * violation or a deadlock (which states it expanded is then not a level
+ * boundary: search with RMC_FLAG_CONTINUE; the other three calls still work). */
+#define RMC_NO_STATE UINT64_MAX
+typedef struct rmc_edge {
+    uint64_t src, dst;         /* store indices                                    */
+    int32_t family, instance;  /* rmc_succ_view's                                  */
+} rmc_edge;                    /* 24 B */
+int rmc_get_levels(const rmc_ctx* ctx, uint64_t* starts, size_t cap, size_t* n);
+int rmc_read_states(rmc_ctx* ctx, uint64_t first, size_t n, rmc_state_view* states, uint64_t* keys);
+int rmc_find_states(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint64_t* index);
+int rmc_graph_edges(rmc_ctx* ctx, uint64_t lo, uint64_t hi, rmc_edge* out, size_t cap, size_t* n_out);
 
 /* ---- simulation (TLC -simulate; Smokeraft.cfg, config 4) ---------------------
  * Replaces TLC's Simulator: random behaviours, each from a random initial state

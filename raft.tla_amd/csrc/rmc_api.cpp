@@ -494,8 +494,15 @@ static int start_run(rmc_ctx* c, int* depth) {
 int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     if (!c) return RMC_E_INVAL;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->wide) return run_bfs_wide(c, cb, user);
-    if (c->dist.on) return run_bfs_sharded(c, cb, user);
+    // the state graph calls (rmc_graph.cpp) read a completed run only: its index is built on demand
+    c->run_done = 0;
+    c->graph_idx = 0;
+    c->run_seed = c->cfg.seed;
+    if (c->wide || c->dist.on) {
+        const int rc = c->wide ? run_bfs_wide(c, cb, user) : run_bfs_sharded(c, cb, user);
+        c->run_done = rc == 0;
+        return rc;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const bool resume = c->resume != 0;  // rmc_recover restored store, set and counters
     c->resume = 0;
@@ -648,6 +655,8 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         fprintf(stderr, "[rmc] lane walk: %llu slots visited, %llu generated, %llu probes: efficiency %.4f\n",
                 (unsigned long long)c->walked, (unsigned long long)c->res.generated,
                 (unsigned long long)c->res.probes, c->walked ? G / (double)c->walked : 0.0);
+    c->run_done = 1;
+    c->graph_idx = c->sh.verify ? 1 : 0;  // verification published every stored state (k_publish)
     return 0;
 }
 

@@ -155,6 +155,13 @@ struct rmc_ctx {
     rmc_violations viol{};
     rmc::u64 viol_least[RMC_INV_COUNT] = {};
     int viol_valid = 0;
+    // state graph export (rmc_graph.cpp): a completed rmc_run_bfs whose store, links and set the
+    // calls may read; its fingerprint salt (rmc_set_seed may change cfg.seed after it); and whether
+    // B.sidx maps every stored state's set slot to its index — a verification run leaves it so, any
+    // other ctx builds it at its first graph call (one k_publish pass); every rmc_run_bfs resets both
+    int run_done = 0;
+    int graph_idx = 0;
+    rmc::u64 run_seed = 0;
     rmc_result res{};
     std::string err;
     std::vector<rmc::u64> level_start;  // level d (1-based) = [level_start[d-1], level_start[d])

@@ -74,7 +74,8 @@ struct DevBufs {
     const u32* rep;
     // full-state verification mode: store index of the state owning each
     // fingerprint-set slot (~0 = not yet published; published between launches
-    // by k_publish) and the deferred hits {parent index, slot | lane << 56}
+    // by k_publish) and the deferred hits {parent index, slot | lane << 56}.  The state graph calls
+    // (rmc_graph.cpp) allocate and publish sidx on a ctx without the mode too, after a run
     u64* sidx;
     u64* vbuf;
     u64 vcap;                  // records in vbuf
@@ -99,6 +100,12 @@ struct Shape {
     int S, K;
     bool sym;
     bool verify;  // full-state verification (single GPU)
+};
+
+// One edge of the state graph (k_graph_edges): rmc.h's rmc_edge, field for field.
+struct GraphEdge {
+    u64 src, dst;  // store indices; dst ~0: the set does not hold the successor's key (an error)
+    int family, instance;
 };
 
 // Simulation counters (k_simulate).
@@ -150,6 +157,15 @@ struct ShapeKernels {
     hipError_t (*keys)(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u64* keys,
                        const u32* ref, unsigned char* same, hipStream_t st);
     hipError_t (*set_salt)(u64 salt, u64 epoch, hipStream_t st);  // epoch << 56; returns after the copies
+    // the state graph (rmc_dev_graph.h; B.sidx published for every stored state): cnt[i - lo] = the
+    // edges out of stored state i of [lo, hi); those edges at out[off[i - lo] ..] (off: the exclusive
+    // scan of cnt, launch_graph_scan), err: min (src << 8 | lane) of an edge without its key in the
+    // set; index[t] = the store index of the stored state with staged state in[t]'s key, or ~0
+    hipError_t (*graph_count)(const Params& P, const DevBufs& B, u64 lo, u64 hi, u32* cnt, hipStream_t st);
+    hipError_t (*graph_edges)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi,
+                              const u64* off, GraphEdge* out, u64 cap, unsigned long long* err, hipStream_t st);
+    hipError_t (*graph_find)(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, const u32* in, u64 n,
+                             u64* index, hipStream_t st);
 };
 // The table of shape (S, K), defined by its object (rmc_kernels_shape.hip), and its lookup:
 // nullptr for a shape that is not built.  The tables are filled when the library loads: not
@@ -201,6 +217,8 @@ hipError_t set_fp_salt(const ShapeKernels& k, u64 seed, u32 set_epoch, hipStream
 
 // Sets bytes [p, p + bytes) to `byte` (the fingerprint set's clear; RMC_FILL=0: hipMemsetAsync).
 hipError_t launch_fill(void* p, u64 bytes, uint8_t byte, hipStream_t st);
+// off[0 .. n] = the exclusive scan of cnt[0 .. n) (off[n]: the total), one block.
+hipError_t launch_graph_scan(const u32* cnt, u64 n, u64* off, hipStream_t st);
 // Random-probe microbenchmark over table[mask + 1] (mode 0 loads, 1 CAS).
 hipError_t launch_probe_bench(u64* table, u64 mask, u64 threads, u32 iters, int mode, u64* sink, hipStream_t st);
 

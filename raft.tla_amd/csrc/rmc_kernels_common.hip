@@ -287,6 +287,36 @@ hipError_t launch_probe_bench(u64* table, u64 mask, u64 threads, u32 iters, int 
     return hipGetLastError();
 }
 
+// The exclusive scan of the per-state edge counts of one chunk of the graph walk (at most
+// a few hundred thousand states): one block, each thread sums a contiguous part, the parts'
+// sums are scanned in LDS, and each thread writes its part's offsets.  off has n + 1 entries.
+__global__ __launch_bounds__(1024) void k_graph_scan(const u32* __restrict__ cnt, u64 n, u64* __restrict__ off) {
+    __shared__ u64 s_sum[1024];
+    const u64 per = (n + 1023) / 1024;
+    const u64 a = threadIdx.x * per < n ? threadIdx.x * per : n, b = a + per < n ? a + per : n;
+    u64 s = 0;
+    for (u64 q = a; q < b; ++q) s += cnt[q];
+    s_sum[threadIdx.x] = s;
+    __syncthreads();
+    for (unsigned d = 1; d < 1024; d <<= 1) {
+        const u64 v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    u64 base = s_sum[threadIdx.x] - s;
+    for (u64 q = a; q < b; ++q) {
+        off[q] = base;
+        base += cnt[q];
+    }
+    if (threadIdx.x == 1023) off[n] = s_sum[1023];
+}
+
+hipError_t launch_graph_scan(const u32* cnt, u64 n, u64* off, hipStream_t st) {
+    hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, cnt, n, off);
+    return hipGetLastError();
+}
+
 // One round of resident blocks of kernel `k` on this device (blocks per CU at
 // its register / LDS occupancy x CUs), cached per kernel and device: 1024 for
 // the 4-wave sorted kernels, 1280 for the 5-wave every-lane kernel (a fixed

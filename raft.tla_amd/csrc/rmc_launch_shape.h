@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "rmc_dev_expand.h"
+#include "rmc_dev_graph.h"
 #include "rmc_dev_sharded.h"
 #include "rmc_dev_tools.h"
 #include "rmc_dev_verify.h"
@@ -159,6 +160,16 @@ static hipError_t launch_expand_dist(bool sym, bool verify, const Params& P, con
     return expansion<S, K>(&k_expand_dist<S, K, 5, false, S >= 4 ? 5 : 6>, kPresorted | C, 0, P, PT, B, lo, hi, st);
 }
 
+// The edges out of the stored states [lo, hi) (k_graph_edges): kBatch probes in flight per
+// thread, as the every-lane expansion kernels keep.
+template <int S, int K>
+static hipError_t launch_graph_edges_t(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, u64 lo,
+                                       u64 hi, const u64* off, GraphEdge* out, u64 cap, unsigned long long* err,
+                                       hipStream_t st) {
+    return launch_n(sym ? k_graph_edges<S, K, true, kBatch> : k_graph_edges<S, K, false, kBatch>, hi - lo, kStrided,
+                    st, P, PT, B, lo, hi, off, out, cap, err);
+}
+
 // The salt and the set epoch of this object's kernels (raft_packed.h c_fp_salt, c_set_ep).
 static hipError_t set_object_salt(u64 salt, u64 epoch, hipStream_t st) {
     // staged on this call's stack and waited for: concurrent callers (one host
@@ -236,6 +247,15 @@ static ShapeKernels shape_table() {
     k.check = launch_check_t<S, K>;
     k.keys = launch_keys_t<S, K>;
     k.set_salt = set_object_salt;
+    k.graph_count = [](const Params& P, const DevBufs& B, u64 lo, u64 hi, u32* cnt, hipStream_t st) {
+        return launch_n(k_graph_count<S, K>, hi - lo, kStrided, st, P, B, lo, hi, cnt);
+    };
+    k.graph_edges = launch_graph_edges_t<S, K>;
+    k.graph_find = [](bool sym, const Params& P, const PermTable& PT, const DevBufs& B, const u32* in, u64 n,
+                      u64* index, hipStream_t st) {
+        return launch_n(sym ? k_graph_find<S, K, true> : k_graph_find<S, K, false>, n, kPerBlock, st, P, PT, B, in, n,
+                        index);
+    };
     return k;
 }
 

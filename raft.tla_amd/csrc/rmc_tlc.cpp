@@ -6,6 +6,7 @@
 // state graph", "Error: Invariant ... is violated", "State N:") keep working.
 // It is the host side above the C ABI (include/rmc.h); Java users bind the
 // same symbols through Panama.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <unistd.h>
 
 #include "../../include/rmc.h"
+#include "rmc_dump.h"
 
 namespace {
 
@@ -75,7 +77,10 @@ std::string msg(const rmc_msg_view& m) {
     return s + ", msource |-> " + srv(m.msource) + ", mdest |-> " + srv(m.mdest) + "]";
 }
 
-void print_state(const rmc_state_view& v) {
+// The state as TLC prints it: one "/\ var = value" line per variable.
+std::string state_text(const rmc_state_view& v) {
+    std::string out;
+    auto line = [&](const char* var, const std::string& value) { out += std::string("/\\ ") + var + " = " + value + "\n"; };
     const int S = v.n_servers;
     std::string bag = v.n_msgs ? "(" : "<<>>";
     for (int q = 0; q < v.n_msgs; ++q) {
@@ -83,22 +88,20 @@ void print_state(const rmc_state_view& v) {
         bag += msg(v.msgs[q]) + " :> " + std::to_string(v.msgs[q].count);
     }
     if (v.n_msgs) bag += ")";
-    printf("/\\ messages = %s\n", bag.c_str());
-    printf("/\\ currentTerm = %s\n", fn(S, [&](int i) { return std::to_string(v.currentTerm[i]); }).c_str());
-    printf("/\\ state = %s\n", fn(S, [&](int i) { return std::string(kRoles[v.state[i]]); }).c_str());
-    printf("/\\ votedFor = %s\n",
-           fn(S, [&](int i) { return v.votedFor[i] < 0 ? std::string("Nil") : srv(v.votedFor[i]); }).c_str());
-    printf("/\\ log = %s\n", fn(S, [&](int i) { return seq(v.log[i], v.log_len[i]); }).c_str());
-    printf("/\\ commitIndex = %s\n", fn(S, [&](int i) { return std::to_string(v.commitIndex[i]); }).c_str());
-    printf("/\\ votesResponded = %s\n", fn(S, [&](int i) { return set_of(v.votesResponded[i], S); }).c_str());
-    printf("/\\ votesGranted = %s\n", fn(S, [&](int i) { return set_of(v.votesGranted[i], S); }).c_str());
-    printf("/\\ nextIndex = %s\n", fn(S, [&](int i) {
-               return fn(S, [&](int j) { return std::to_string(v.nextIndex[i][j]); });
-           }).c_str());
-    printf("/\\ matchIndex = %s\n", fn(S, [&](int i) {
-               return fn(S, [&](int j) { return std::to_string(v.matchIndex[i][j]); });
-           }).c_str());
+    line("messages", bag);
+    line("currentTerm", fn(S, [&](int i) { return std::to_string(v.currentTerm[i]); }));
+    line("state", fn(S, [&](int i) { return std::string(kRoles[v.state[i]]); }));
+    line("votedFor", fn(S, [&](int i) { return v.votedFor[i] < 0 ? std::string("Nil") : srv(v.votedFor[i]); }));
+    line("log", fn(S, [&](int i) { return seq(v.log[i], v.log_len[i]); }));
+    line("commitIndex", fn(S, [&](int i) { return std::to_string(v.commitIndex[i]); }));
+    line("votesResponded", fn(S, [&](int i) { return set_of(v.votesResponded[i], S); }));
+    line("votesGranted", fn(S, [&](int i) { return set_of(v.votesGranted[i], S); }));
+    line("nextIndex", fn(S, [&](int i) { return fn(S, [&](int j) { return std::to_string(v.nextIndex[i][j]); }); }));
+    line("matchIndex", fn(S, [&](int i) { return fn(S, [&](int j) { return std::to_string(v.matchIndex[i][j]); }); }));
+    return out;
 }
+
+void print_state(const rmc_state_view& v) { fputs(state_text(v).c_str(), stdout); }
 
 const char* inv_name(int bit) {
     switch (bit) {
@@ -161,6 +164,63 @@ void print_coverage(const rmc_coverage& cv) {
     printf("End of statistics.\n");
 }
 
+// -dump: the graph of the finished search, read back from the ctx (rmc.h "state graph export")
+// and written by rmc_dump.h's writers.  Returns 0, or 1 after printing the error.
+int write_dump(rmc_ctx* ctx, const std::string& file, bool dot, bool labels) {
+    auto bad = [&](const char* what) {
+        printf("Error: -dump: %s: %s\n", what, rmc_last_error(ctx));
+        return 1;
+    };
+    size_t nl = 0;
+    if (rmc_get_levels(ctx, nullptr, 0, &nl)) return bad("rmc_get_levels");
+    std::vector<uint64_t> starts(nl);
+    if (rmc_get_levels(ctx, starts.data(), nl, &nl)) return bad("rmc_get_levels");
+    const uint64_t distinct = nl ? starts[nl - 1] : 0;
+    std::vector<rmc_dump::Node> nodes(distinct);
+    {
+        const uint64_t chunk = 1024;
+        std::vector<rmc_state_view> st((size_t)std::min<uint64_t>(chunk, distinct));
+        std::vector<uint64_t> keys(st.size());
+        size_t level = 1;  // level L = [starts[L - 1], starts[L])
+        for (uint64_t a = 0; a < distinct; a += chunk) {
+            const size_t m = (size_t)std::min<uint64_t>(chunk, distinct - a);
+            if (rmc_read_states(ctx, a, m, st.data(), keys.data())) return bad("rmc_read_states");
+            for (size_t t = 0; t < m; ++t) {
+                while (a + t >= starts[level]) ++level;
+                nodes[a + t] = rmc_dump::Node{keys[t], (int)level, state_text(st[t])};
+            }
+        }
+    }
+    std::vector<rmc_dump::Edge> edges;
+    if (dot) {
+        std::vector<rmc_edge> buf(1u << 20);
+        const uint64_t chunk = 1u << 16;
+        for (uint64_t a = 0; a < distinct; a += chunk) {
+            const uint64_t b = std::min<uint64_t>(distinct, a + chunk);
+            size_t n = 0;
+            if (rmc_graph_edges(ctx, a, b, buf.data(), buf.size(), &n)) return bad("rmc_graph_edges");
+            if (n > buf.size()) {
+                buf.resize(n);
+                if (rmc_graph_edges(ctx, a, b, buf.data(), buf.size(), &n)) return bad("rmc_graph_edges");
+            }
+            for (size_t q = 0; q < n; ++q) edges.push_back(rmc_dump::Edge{buf[q].src, buf[q].dst, buf[q].family, buf[q].instance});
+        }
+    }
+    FILE* f = fopen(file.c_str(), "w");
+    if (!f) {
+        printf("Error: -dump: cannot write %s\n", file.c_str());
+        return 1;
+    }
+    const bool ok = dot ? rmc_dump::write_dot(f, nodes, edges, kFamilies, 10, labels) : rmc_dump::write_states(f, nodes);
+    if (fclose(f) != 0 || !ok) {
+        printf("Error: -dump: writing %s failed\n", file.c_str());
+        return 1;
+    }
+    if (dot) printf("State graph written to %s (%zu states, %zu transitions).\n", file.c_str(), nodes.size(), edges.size());
+    else printf("States written to %s (%zu states).\n", file.c_str(), nodes.size());
+    return 0;
+}
+
 int progress(const rmc_level_stats* s, void*) {
     printf("Progress(%d) at %.2fs: %llu states generated, %llu distinct states found, %llu states left on queue.\n",
            s->level + 1, s->seconds, (unsigned long long)s->generated, (unsigned long long)s->distinct,
@@ -174,7 +234,15 @@ int usage() {
             "usage: rmc-tlc [-config X.cfg] [-depth N] [-deadlock] [-device D] [-capacity N] [-workers N]\n"
             "               [-verify] [-fpseed S] [-checkpoint F] [-recover F] [-simulate [num=N]] [-seed S]\n"
             "               [-raft raft.tla] [-builtin-raft] [-gpus N] [-nospill] [-window N] [-fpmem B]\n"
-            "               [-coverage [minutes]] [-continue] X.tla\n"
+            "               [-coverage [minutes]] [-continue] [-dump [dot[,actionlabels]] FILE] X.tla\n"
+            "  -dump FILE     write every distinct state found to FILE (TLC -dump)\n"
+            "  -dump dot[,actionlabels] FILE  write the state graph to FILE in GraphViz dot format: a node per\n"
+            "             state (its id the state's fingerprint), an edge per transition, labelled with its\n"
+            "             action under actionlabels; colorize and snapshot are not supported.  FILE is\n"
+            "             written as named (no extension is added).  Implies -nospill, and -capacity 2^26\n"
+            "             unless given (the graph's state index takes 8 B per fingerprint-set slot);\n"
+            "             single GPU, packed layout; not with -gpus N > 1, -simulate or -recover.  The\n"
+            "             edges need a search that did not stop at a violation: use -continue\n"
             "  -continue      search past invariant violations (TLC -continue): violating states are kept\n"
             "             and expanded; after the search every violated invariant is reported with the\n"
             "             trace to its first state and the number of states that violate it (single\n"
@@ -276,6 +344,8 @@ int main(int argc, char** argv) {
     uint32_t fopts = 0;
     unsigned long long capacity = 0, window = 0, fpmem = 0;
     int nospill = 0, coverage = 0, cont = 0;
+    std::string dump;  // -dump's FILE
+    int dump_dot = 0, dump_labels = 0;
     for (int a = 1; a < argc; ++a) {
         std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : nullptr; };
@@ -289,6 +359,31 @@ int main(int argc, char** argv) {
         else if (s == "-verify") verify = 1;
         else if (s == "-nospill") nospill = 1;
         else if (s == "-continue") cont = 1;
+        else if (s == "-dump") {  // TLC: -dump FILE, or -dump dot[,option...] FILE
+            const char* v = next();
+            if (!v) return usage();
+            std::string f = v;
+            if (f == "dot" || f.compare(0, 4, "dot,") == 0) {
+                dump_dot = 1;
+                for (size_t p = 3; p < f.size();) {
+                    const size_t e = f.find(',', p + 1);
+                    const std::string opt = f.substr(p + 1, e == std::string::npos ? e : e - p - 1);
+                    if (opt == "actionlabels") dump_labels = 1;
+                    else if (opt == "colorize" || opt == "snapshot") {
+                        fprintf(stderr, "-dump dot: the option %s is not supported (actionlabels is)\n", opt.c_str());
+                        return usage();
+                    } else {
+                        fprintf(stderr, "-dump dot: unknown option %s\n", opt.c_str());
+                        return usage();
+                    }
+                    p = e == std::string::npos ? f.size() : e;
+                }
+                v = next();
+                if (!v) return usage();
+                f = v;
+            }
+            dump = f;
+        }
         else if (s == "-coverage") {  // TLC's optional interval in minutes: a number, not the model
             coverage = 1;
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9' &&
@@ -330,6 +425,12 @@ int main(int argc, char** argv) {
                 gpus > 1 ? "-gpus N > 1" : !ckpt.empty() ? "-checkpoint" : !recover.empty() ? "-recover" : "-simulate");
         return usage();
     }
+    if (!dump.empty() && (gpus > 1 || simulate || !recover.empty())) {
+        fprintf(stderr, "-dump writes the graph of one whole single-GPU search: not with %s\n",
+                gpus > 1 ? "-gpus N > 1" : simulate ? "-simulate" : "-recover");
+        return usage();
+    }
+    if (!dump.empty()) nospill = 1;  // the graph is read from the resident store
     if (cfg.empty()) cfg = (tla.size() > 4 && tla.substr(tla.size() - 4) == ".tla" ? tla.substr(0, tla.size() - 4) : tla) + ".cfg";
     printf("rmc-tlc: %s\n", rmc_version());
     if (const char* b = getenv("RMC_BUILTIN_RAFT")) if (b[0] == '1') fopts |= RMC_FRONT_BUILTIN_RAFT;
@@ -360,6 +461,13 @@ int main(int argc, char** argv) {
     // layout compares with resident records only (it refuses the two flags together),
     // nor under -continue, whose pass reads every stored state's record
     const bool wide = rmc_state_bytes(&c) > 64 * 4;  // (a packed state is at most 18 words)
+    if (!dump.empty() && wide) {
+        printf("Error: -dump reads the graph of the packed layout: this model runs on the wide layout (bounds "
+               "beyond the packed capacity, or fields no CONSTRAINT bounds)\n");
+        return 1;
+    }
+    // the graph's slot -> state index takes as much HBM as the set: not beside an auto-sized one
+    if (!dump.empty() && !capacity && !fpmem) c.state_capacity = 1ull << 26;
     if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && (verify || cont)))
         c.flags |= RMC_FLAG_SPILL;
     c.device_window = window;
@@ -563,6 +671,7 @@ int main(int argc, char** argv) {
         else printf("Checkpoint written to %s (%llu states on the queue).\n", ckpt.c_str(),
                     (unsigned long long)r.left_on_queue);
     }
+    if (!dump.empty() && write_dump(ctx, dump, dump_dot != 0, dump_labels != 0) && !exitcode) exitcode = 1;
     if (recover.empty())
         printf("Finished in %.0fms (%.0f distinct states/s)\n", r.seconds * 1e3, r.distinct / (r.seconds > 0 ? r.seconds : 1));
     else

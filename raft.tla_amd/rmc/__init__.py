@@ -137,6 +137,14 @@ class Violations(C.Structure):
                 ("depth", C.c_int32 * INV_COUNT)]
 
 
+NO_STATE = (1 << 64) - 1  # RMC_NO_STATE: rmc_find_states found no stored state with the key
+
+
+class Edge(C.Structure):
+    """rmc_edge: one transition of the state graph; src and dst are store indices."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("family", C.c_int32), ("instance", C.c_int32)]
+
+
 class Transport(C.Structure):
     _fields_ = [("user", C.c_void_p), ("alltoallv", ALLTOALLV_FN), ("allgather", ALLGATHER_FN)]
 
@@ -147,7 +155,8 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_set_seed", "rmc_simulate", "rmc_sim_replay", "rmc_set_fp_bits",
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
            "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action",
-           "rmc_check_states", "rmc_state_keys", "rmc_get_violations", "rmc_trace_violation")
+           "rmc_check_states", "rmc_state_keys", "rmc_get_violations", "rmc_trace_violation",
+           "rmc_get_levels", "rmc_read_states", "rmc_find_states", "rmc_graph_edges")
 
 _lib = None
 
@@ -230,6 +239,16 @@ def native():
         lib.rmc_state_keys.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
         lib.rmc_state_keys.restype = C.c_int
+        lib.rmc_get_levels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.rmc_get_levels.restype = C.c_int
+        lib.rmc_read_states.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(StateView),
+                                        C.POINTER(C.c_uint64)]
+        lib.rmc_read_states.restype = C.c_int
+        lib.rmc_find_states.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.rmc_find_states.restype = C.c_int
+        lib.rmc_graph_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(Edge), C.c_size_t,
+                                        C.POINTER(C.c_size_t)]
+        lib.rmc_graph_edges.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -323,6 +342,18 @@ def probe_bench(device=0, table_bytes=64 << 30, accesses=1 << 31, mode=0):
     return rate.value
 
 
+class _ProgressRows(list):
+    """What run() leaves in Checker.levels: the progress callback's rows, as before —
+    and, called, Checker.levels() (the attribute has shadowed the method since run())."""
+
+    def __init__(self, rows, checker):
+        super().__init__(rows)
+        self._checker = checker
+
+    def __call__(self):
+        return Checker.levels(self._checker)
+
+
 class Checker:
     """One model-checking context on one GPU (rmc_ctx)."""
 
@@ -364,7 +395,7 @@ class Checker:
         self._check(self.lib.rmc_run_bfs(self.ctx, fn, None))
         res = Result()
         self._check(self.lib.rmc_get_result(self.ctx, C.byref(res)))
-        self.levels = levels
+        self.levels = _ProgressRows(levels, self)
         return res
 
     def simulate(self, behaviours=1 << 20, depth=100, smoke_k=2, smoke_nat=2, seed=0, mode=0) -> SimResult:
@@ -484,3 +515,44 @@ class Checker:
         same = (C.c_uint8 * len(views))()
         self._check(self.lib.rmc_state_keys(self.ctx, arr, len(views), keys, refs, same))
         return list(keys), list(same)
+
+    # ---- the state graph of the last completed run() (rmc.h "state graph export") ----
+    def levels(self):
+        """rmc_get_levels: starts[l] = the store index of the first state of level
+        l + 1; the last entry = distinct."""
+        n = C.c_size_t()
+        self._check(self.lib.rmc_get_levels(self.ctx, None, 0, C.byref(n)))
+        starts = (C.c_uint64 * n.value)()
+        self._check(self.lib.rmc_get_levels(self.ctx, starts, n.value, C.byref(n)))
+        return list(starts)
+
+    def read_states(self, first, n, keys=False):
+        """rmc_read_states: the stored states [first, first + n) as a ctypes array of
+        StateView; keys=True: (states, keys), the key the search inserted for each."""
+        st = (StateView * n)()
+        ks = (C.c_uint64 * n)() if keys else None
+        self._check(self.lib.rmc_read_states(self.ctx, first, n, st, ks))
+        return (st, list(ks)) if keys else st
+
+    def find_states(self, views):
+        """rmc_find_states: per view the store index of the stored state with its key
+        (under symmetry=True: of its orbit's stored representative), or NO_STATE.
+        `views`: a sequence of StateView, or a ctypes array of them (passed as it is)."""
+        arr = views if isinstance(views, C.Array) else (StateView * len(views))(*views)
+        index = (C.c_uint64 * len(views))()
+        self._check(self.lib.rmc_find_states(self.ctx, arr, len(views), index))
+        return list(index)
+
+    def graph_edges(self, lo, hi, cap=None):
+        """rmc_graph_edges: every edge out of the stored states [lo, hi), in (src,
+        instance) order, as a ctypes array of Edge.  cap: the room offered (default:
+        what the range needs); returns (edges written, n_out) then."""
+        n = C.c_size_t()
+        if cap is not None:
+            out = (Edge * max(1, cap))()
+            self._check(self.lib.rmc_graph_edges(self.ctx, lo, hi, out, cap, C.byref(n)))
+            return out[:min(cap, n.value)], n.value
+        self._check(self.lib.rmc_graph_edges(self.ctx, lo, hi, None, 0, C.byref(n)))
+        out = (Edge * max(1, n.value))()
+        self._check(self.lib.rmc_graph_edges(self.ctx, lo, hi, out, n.value, C.byref(n)))
+        return out[:n.value]

@@ -24,12 +24,14 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 14 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 15 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
                               rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys; 12: RMC_FLAG_CONTINUE,
                               rmc_violations, rmc_get_violations, rmc_trace_violation; 13: RMC_FLAG_SYMMETRY on the wide
                               layout (depth-bounded runs), rmc_state_keys on a wide ctx under it; 14: the state
-                              graph: rmc_get_levels, rmc_read_states, rmc_find_states, rmc_graph_edges */
+                              graph: rmc_get_levels, rmc_read_states, rmc_find_states, rmc_graph_edges; 15: model-defined
+                              invariants: RMC_FRONT_PREDICATES, rmc_predicates_from_files, rmc_set_predicates,
+                              rmc_eval_predicates, rmc_predicate_error, RMC_INV_USER0 */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -666,9 +668,70 @@ int rmc_probe_bench(int device, uint64_t table_bytes, uint64_t accesses, int mod
  * as shipped (MCraft.cfg:1-39) — is accepted with the RMC_FLAG_UNBOUNDED_*
  * bits set (rmc_create then requires max_depth > 0). */
 #define RMC_FRONT_DEPTH_BOUNDED (1u << 2)
+/* RMC_FRONT_PREDICATES: an INVARIANT whose name is not one of the compiled-in ten is
+ * accepted (not put in rmc_config.invariants): the caller promises to compile it with
+ * rmc_predicates_from_files and hand it to the ctx with rmc_set_predicates.  The ten
+ * known names keep their digest rule. */
+#define RMC_FRONT_PREDICATES (1u << 3)
 int rmc_model_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
                          uint32_t options, rmc_config* cfg, rmc_sim_config* sim,
                          char* info, size_t info_cap);
+/* ---- model-defined invariants ------------------------------------------------------
+ * A state predicate the model defines and its .cfg names under INVARIANT, other than
+ * the ten compiled-in ones, is compiled by the front-end to a small bytecode program
+ * and evaluated by a pass of its own on every state the BFS stores (after the seed and
+ * after each expansion launch; the expansion kernels and the fused check are unchanged;
+ * without predicates nothing is allocated, launched or read back for them).
+ *
+ * The language (DESIGN.md "Model-defined invariants" has the grammar): a typed subset
+ * of TLA+ over raft.tla's variables in which every value is a 32-bit integer —
+ * Booleans, naturals, servers (Nil = -1), roles, message types, sets of servers.
+ * Atoms: integers, TRUE, FALSE, Nil, Follower, Candidate, Leader, the four message
+ * types, the cfg's integer constants, server model values, Server, Quorum (to the right
+ * of \in or as a quantifier's domain).  State reads: currentTerm[e], state[e],
+ * votedFor[e], commitIndex[e], votesResponded[e], votesGranted[e], nextIndex[e][e],
+ * matchIndex[e][e], Len(log[e]), LastTerm(log[e]), log[e][n].term, log[e][n].value,
+ * messages[m], and the scalar fields of a bound message m.  Operators: /\ \/ ~ => <=>
+ * (infix and as bulleted lists), = /= # < <= =< \leq > >= \geq, + -, IF THEN ELSE, \in,
+ * \notin, {a, b}, {x \in D : P}, \cup \cap \ \subseteq, Cardinality.  Quantifiers \A \E
+ * over Server, a server-set expression, Quorum, a..b, DOMAIN log[e], DOMAIN messages.
+ * The model's own operator definitions are expanded in place (no recursion).  Everything
+ * else is refused when compiled, with the construct, its line and column.
+ * Evaluation is left to right with short circuit, as in TLC; a read outside a domain is
+ * an evaluation error, as in TLC.  A verdict is 0 (holds), 1 (violated), 2 (error).
+ *
+ * rmc_predicates_from_files: rmc_model_from_files' arguments (options without
+ * RMC_FRONT_PREDICATES too); compiles exactly the INVARIANTs rmc_model_from_files would
+ * accept only under RMC_FRONT_PREDICATES, in cfg order, at most RMC_MAX_PREDICATES (1024
+ * code words, stack depth 16, 8 bound names: more is refused with the count).  A model
+ * with none gives a program of count 0.  RMC_E_PARSE with the message in err.
+ * rmc_set_predicates copies the program into the ctx (NULL, or a program of count 0,
+ * removes it).  rmc_run_bfs then reports a violated predicate p like a built-in
+ * invariant: violated_inv = RMC_INV_USER0 << p, violation_depth, rmc_trace; the level is
+ * finished first, the least store index wins over the fused check's and the pass's, at
+ * equal index the built-in; rmc_predicate_error tells a violation from an evaluation
+ * error.  Counts of a run whose predicates hold equal the run without them.
+ * Single GPU; packed layout resident and with RMC_FLAG_SPILL; wide layout resident; with
+ * RMC_FLAG_SYMMETRY, RMC_FLAG_VERIFY_STATES, RMC_FLAG_COVERAGE.  RMC_E_INVAL: a ctx with
+ * RMC_FLAG_CONTINUE (its tallies have ten rows), a sharded ctx (and rmc_shard after
+ * predicates are set), a wide ctx with RMC_FLAG_SPILL (the unstored last level), under
+ * RMC_FLAG_SYMMETRY a predicate that names a server model value, a program compiled
+ * for another n_servers.  With predicates set rmc_simulate, rmc_checkpoint and
+ * rmc_recover are RMC_E_STATE.
+ * rmc_eval_predicates (test hook): the same device interpreter on n caller states,
+ * verdicts[t * count + p] for every predicate, none skipped. */
+#define RMC_MAX_PREDICATES 8
+#define RMC_INV_USER0 (1u << 16)      /* predicate p is bit 16 + p of rmc_result.violated_inv */
+typedef struct rmc_predicates rmc_predicates;
+int rmc_predicates_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                              uint32_t options, rmc_predicates** out, char* err, size_t err_cap);
+void rmc_predicates_free(rmc_predicates* p);
+int rmc_predicates_count(const rmc_predicates* p);
+const char* rmc_predicates_name(const rmc_predicates* p, int index);
+int rmc_set_predicates(rmc_ctx* ctx, const rmc_predicates* p);
+int rmc_eval_predicates(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint8_t* verdicts);
+int rmc_predicate_error(const rmc_ctx* ctx);  /* 1 if the reported violation is an evaluation error */
+
 /* rmc_model_from_files for BFS / simulation models with raft_path = NULL and
  * RMC_FRONT_BUILTIN_RAFT taken from the environment (RMC_BUILTIN_RAFT=1).
  * `tla_path` may be NULL (the module next to cfg_path with the same stem). */

@@ -256,6 +256,8 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
     }
     c->res.distinct = k.count;
     scan_target(c, &k, 1, *depth);
+    if (pred_on(c))
+        if (int rc = pred_scan(c, *depth)) return rc;
     if (cb) {
         rmc_level_stats ls{};
         ls.level = nnew ? *depth - 1 : *depth;
@@ -448,6 +450,7 @@ void rmc_destroy(rmc_ctx* c) {
     (void)hipFree(c->B.ties);
     (void)hipFree(c->d_cov);
     (void)hipFree(c->d_viol);
+    pred_free(c);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -475,6 +478,8 @@ static int start_run(rmc_ctx* c, int* depth) {
         if (int rc = cover_begin(c)) return rc;
     if (continue_on(c))
         if (int rc = viol_begin(c)) return rc;
+    if (pred_on(c))
+        if (int rc = pred_begin(c)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
@@ -488,6 +493,10 @@ static int start_run(rmc_ctx* c, int* depth) {
         HIPCHK(c, c->k->cover(c->P, c->B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
     if (continue_on(c))  // the seed's states
         HIPCHK(c, c->k->violations(c->P, c->B, 0, c->h_ctr->count, c->d_viol, c->st));
+    if (pred_on(c)) {  // the seed's states: a predicate Init fails is the target, at depth 1
+        if (int rc = pred_pass(c, 0, c->h_ctr->count)) return rc;
+        if (int rc = pred_scan(c, 1)) return rc;
+    }
     return 0;
 }
 
@@ -512,6 +521,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     c->viol_valid = 0;
     const bool cover = cover_on(c);  // (rmc_recover refuses the flags: never a resumed run)
     const bool cont = continue_on(c);
+    const bool preds = pred_on(c);  // (rmc_recover refuses a ctx with predicates too)
     int depth = 0;
     if (resume) {
         c->res.left_on_queue = 0;
@@ -621,19 +631,21 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     c->res.spills = cnt / win;  // passes of the ring
                 }
             }
-            if (cover || cont) {
+            if (cover || cont || preds) {
                 // the coverage pass of this launch: its parents [a, b) are still resident
                 // (the store; the linear window, which moves only [base, a) and before the
                 // launch; the ring, whose room is relative to a), and the states it added
                 // are [count before, count after) — after k_ties, Publish / Verify.  The
-                // violation pass reads those states: resident too (ring_room keeps a
-                // launch's new states inside the window)
+                // violation pass and the predicate pass read those states: resident too
+                // (ring_room keeps a launch's new states inside the window)
                 if (!c->sh.verify && !c->spill.on) {  // (those paths have read the counters)
                     if (int rc = read_counters(c)) return rc;
                     if (c->h_ctr->overflow || c->h_ctr->table_full) break;
                 }
                 if (cover) HIPCHK(c, c->k->cover(c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
                 if (cont) HIPCHK(c, c->k->violations(c->P, c->B, cov_before, c->h_ctr->count, c->d_viol, c->st));
+                if (preds)
+                    if (int rc = pred_pass(c, cov_before, c->h_ctr->count)) return rc;
             }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
@@ -797,6 +809,9 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
         (sc->mode != RMC_SIM_WITHIN_CAPACITY && sc->mode != RMC_SIM_TRUNCATE && sc->mode != RMC_SIM_TLC))
         return RMC_E_INVAL;
     HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (pred_on(c))
+        return fail(c, RMC_E_STATE, "simulation does not evaluate model-defined invariants (rmc_set_predicates(ctx, NULL) "
+                                    "removes them)");
     if (c->wide) return sim_wide(c, sc, out, rec_beh, wrec);
     if (sc->mode == RMC_SIM_TLC)
         return fail(c, RMC_E_INVAL, "RMC_SIM_TLC draws on the wide layout only (bounds beyond the packed capacity)");

@@ -75,6 +75,8 @@ extern "C" {
 int rmc_checkpoint(rmc_ctx* c, const char* path) {
     if (!c || !path) return RMC_E_INVAL;
     if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
+    if (pred_on(c))
+        return fail(c, RMC_E_STATE, "checkpoint: not supported with model-defined invariants set (rmc_set_predicates)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_COVERAGE (the tallies are of whole "
                                     "runs and are not written)");
@@ -133,6 +135,8 @@ int rmc_checkpoint(rmc_ctx* c, const char* path) {
 int rmc_recover(rmc_ctx* c, const char* path) {
     if (!c || !path) return RMC_E_INVAL;
     if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
+    if (pred_on(c))
+        return fail(c, RMC_E_STATE, "recover: not supported with model-defined invariants set (rmc_set_predicates)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_COVERAGE (the tallies are of whole runs)");
     if (c->cfg.flags & RMC_FLAG_CONTINUE)

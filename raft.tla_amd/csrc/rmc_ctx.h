@@ -155,6 +155,14 @@ struct rmc_ctx {
     rmc_violations viol{};
     rmc::u64 viol_least[RMC_INV_COUNT] = {};
     int viol_valid = 0;
+    // model-defined invariants (rmc_set_predicates; rmc_pred.h, rmc_pred.cpp): the ctx's copy of the
+    // program and its names, the program in device memory and the pass's word (min over the states
+    // a predicate fails on of index << 8 | predicate << 1 | error), all allocated by
+    // rmc_set_predicates only; whether the violation reported is an evaluation error
+    rmc_predicates* preds = nullptr;
+    rmc::pred::Program* d_prog = nullptr;
+    unsigned long long* d_pword = nullptr;
+    int pred_error = 0;
     // state graph export (rmc_graph.cpp): a completed rmc_run_bfs whose store, links and set the
     // calls may read; its fingerprint salt (rmc_set_seed may change cfg.seed after it); and whether
     // B.sidx maps every stored state's set slot to its index — a verification run leaves it so, any
@@ -221,6 +229,16 @@ int cover_end(rmc_ctx* c);
 inline bool continue_on(const rmc_ctx* c) { return (c->cfg.flags & RMC_FLAG_CONTINUE) != 0; }
 int viol_begin(rmc_ctx* c);
 int viol_end(rmc_ctx* c);
+// Model-defined invariants, both layouts: the word cleared at the start of a run; the pass
+// over the states a launch (or the seed) added, [nlo, nhi); and at a level's end (after
+// scan_target) the word read back and merged with the fused check's target: the least
+// index wins, at equal index the built-in invariant.
+inline bool pred_on(const rmc_ctx* c) { return c->preds != nullptr; }
+int pred_begin(rmc_ctx* c);
+int pred_pass(rmc_ctx* c, rmc::u64 nlo, rmc::u64 nhi);
+int pred_scan(rmc_ctx* c, int depth);
+void pred_free(rmc_ctx* c);
+int pred_eval_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint8_t* d_out);  // rmc_wide.cpp
 // After the seed launch's read_counters, on either layout: level 1 is the states
 // it stored, and an invariant Init violates is the target.  Returns the depth.
 int seed_done(rmc_ctx* c);

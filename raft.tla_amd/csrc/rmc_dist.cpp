@@ -653,6 +653,9 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
     if (!c || world < 1 || world > kMaxWorld || rank < 0 || rank >= world) return RMC_E_INVAL;
     if (!rccl_id && !(host && host->alltoallv && host->allgather))
         return fail(c, RMC_E_INVAL, "rmc_shard needs an RCCL id or a host transport");
+    if (pred_on(c))
+        return fail(c, RMC_E_INVAL, "rmc_shard: model-defined invariants are single-GPU (rmc_set_predicates(ctx, NULL) "
+                                    "removes them)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_COVERAGE (coverage is single GPU)");
     if (c->cfg.flags & RMC_FLAG_CONTINUE)

@@ -25,6 +25,7 @@
 #include <fstream>
 #include <functional>
 #include <map>
+#include <memory>
 #include <regex>
 #include <set>
 #include <sstream>
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "../../include/rmc.h"
+#include "rmc_pred.h"
 
 namespace {
 
@@ -578,6 +580,8 @@ std::string body_location(const Unit& u, const std::string& name, const std::str
            std::to_string(l2) + ", col " + std::to_string(c2) + " of module " + module + ">";
 }
 
+#include "rmc_pred_compile.h"
+
 struct Bounds { int term = -1, log = -1, msgs = -1, dup = -1; };
 
 void set_min(int* dst, int v) { *dst = (*dst < 0 || v < *dst) ? v : *dst; }
@@ -585,9 +589,12 @@ void set_min(int* dst, int v) { *dst = (*dst < 0 || v < *dst) ? v : *dst; }
 }  // namespace
 
 // options: RMC_FRONT_BUILTIN_RAFT (1) accept a model whose raft.tla is not on
-// disk, using the compiled-in one; RMC_FRONT_SIMULATE (2) simulation model.
+// disk, using the compiled-in one; RMC_FRONT_SIMULATE (2) simulation model;
+// RMC_FRONT_PREDICATES (8) accept INVARIANTs of the model's own.  preds != nullptr:
+// compile those into it (rmc_predicates_from_files).
 static int parse_model(const char* cfg_path, const char* tla_path, const char* raft_path, uint32_t options,
-                       rmc_config* out, rmc_sim_config* sim, char* info, size_t info_cap) {
+                       rmc_config* out, rmc_sim_config* sim, char* info, size_t info_cap,
+                       rmc_predicates* preds = nullptr) {
     std::string e;
     auto fail = [&](const std::string& m) {
         if (info && info_cap) snprintf(info, info_cap, "%s", m.c_str());
@@ -692,6 +699,7 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
     if (!value_of("Server", &sv, &server_via) || !set_elems(sv, &elems) || elems.empty())
         return fail("cannot resolve CONSTANT Server to a set literal of model values");
     g.n_servers = (int)elems.size();
+    const std::vector<std::string> server_elems = elems;
     if (std::set<std::string>(elems.begin(), elems.end()).size() != elems.size())
         return fail("CONSTANT Server lists a model value twice");
     if (!value_of("Value", &sv) || !set_elems(sv, &elems) || elems.empty())
@@ -914,6 +922,7 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         {"CandidateTermNotInLog", RMC_INV_CAND_TERM}, {"VotesGrantedInv", RMC_INV_VOTES_GRANTED},
         {"QuorumLogInv", RMC_INV_QUORUM_LOG}, {"MoreUpToDateCorrect", RMC_INV_MORE_UP_TO_DATE},
         {"LeaderCompleteness", RMC_INV_LEADER_COMPLETE}};
+    std::vector<std::string> user_invs;  // RMC_FRONT_PREDICATES: the INVARIANTs that are none of the ten
     for (const auto& in : C.invariants) {
         if (in == "TypeOK") {  // raft.tla:482-492 (checked with raft.tla above)
             g.invariants |= RMC_INV_TYPEOK;
@@ -921,6 +930,11 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         }
         uint32_t bit = 0;
         for (const auto& k : kInv) if (in == k.name) bit = k.bit;
+        if (!bit && (options & RMC_FRONT_PREDICATES)) {  // the model's own: compiled by rmc_predicates_from_files
+            if (!X.def(in)) return fail("INVARIANT " + in + " is not defined by the model");
+            user_invs.push_back(in);
+            continue;
+        }
         if (!bit) return fail("INVARIANT " + in + " is not compiled into the engine");
         const Module* where = nullptr;
         if (!X.def(in, &where))
@@ -947,6 +961,10 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
     else if (!C.check_deadlock.empty() && C.check_deadlock != "TRUE")
         return fail("CHECK_DEADLOCK must be TRUE or FALSE");
     g.flags = flags;
+    if (preds) {
+        std::string why;
+        if (!compile_predicates(X, user_invs, server_elems, elems, preds, &why)) return fail(why);
+    }
     *out = g;
     if (info && info_cap) {
         std::string all;
@@ -965,6 +983,32 @@ extern "C" int rmc_model_from_files(const char* cfg_path, const char* tla_path, 
                                     uint32_t options, rmc_config* cfg, rmc_sim_config* sim, char* info,
                                     size_t info_cap) {
     return parse_model(cfg_path, tla_path, raft_path, options, cfg, sim, info, info_cap);
+}
+
+extern "C" int rmc_predicates_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                                         uint32_t options, rmc_predicates** out, char* err, size_t err_cap) {
+    if (!out) {
+        if (err && err_cap) snprintf(err, err_cap, "null argument");
+        return RMC_E_PARSE;
+    }
+    *out = nullptr;
+    std::unique_ptr<rmc_predicates> p(new rmc_predicates());
+    rmc_config cfg;
+    rmc_sim_config sim;
+    if (int rc = parse_model(cfg_path, tla_path, raft_path, options | RMC_FRONT_PREDICATES, &cfg, &sim, err, err_cap,
+                             p.get()))
+        return rc;
+    if (err && err_cap) err[0] = 0;
+    *out = p.release();
+    return 0;
+}
+
+extern "C" void rmc_predicates_free(rmc_predicates* p) { delete p; }
+
+extern "C" int rmc_predicates_count(const rmc_predicates* p) { return p ? p->prog.n_pred : 0; }
+
+extern "C" const char* rmc_predicates_name(const rmc_predicates* p, int index) {
+    return p && index >= 0 && index < p->prog.n_pred ? p->name[index] : nullptr;
 }
 
 extern "C" int rmc_config_from_files(const char* cfg_path, const char* tla_path, rmc_config* out, char* err,

@@ -7,6 +7,9 @@
 #include "raft_wide.h"
 
 namespace rmc {
+namespace pred {
+struct Program;  // rmc_pred.h: a compiled set of model-defined invariants
+}
 
 // Device-side counters of one BFS level (zeroed/reset by the host per level).
 struct Counters {
@@ -152,6 +155,12 @@ struct ShapeKernels {
     hipError_t (*violations)(const Params& P, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* viol,
                              hipStream_t st);
     hipError_t (*check)(const Params& P, const u32* in, u64 n, int* out, hipStream_t st);
+    // model-defined invariants (k_pred, k_pred_eval, rmc_dev_pred.h; prog: the program in device memory):
+    // the states a launch added, [nlo, nhi), into word = min (index << 8 | predicate << 1 | error) over
+    // the states on which a predicate does not hold; out[t * n_pred + p] = predicate p's verdict on in[t]
+    hipError_t (*pred)(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* word,
+                       hipStream_t st);
+    hipError_t (*pred_eval)(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st);
     // keys[t] = the key of in[t] (P.fp_mask applied); ref != nullptr: same[t] = in[t] compares equal to
     // the record in[ref[t]] (k_keys, rmc_dev_tools.h)
     hipError_t (*keys)(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u64* keys,
@@ -280,6 +289,12 @@ hipError_t launch_wkeys(const WModel& M, const WState* in, u64 n, u64* keys, con
                         u64 salt, hipStream_t st);
 hipError_t launch_wsimulate(const WModel& M, const WState* inits, u64 n_init, u64 n_beh, int depth, u64 seed, int mode,
                             SimCounters* out, i64 rec_beh, WState* rec, hipStream_t st);
+// ShapeKernels::pred on the wide records (k_wpred; the resident store only), and ::pred_eval on
+// staged records of the store's kind (k_wpred_eval; compact: WideBufs.compact's numbering)
+hipError_t launch_wpred(const pred::Program* prog, const WModel& M, const WideBufs& B, u64 nlo, u64 nhi,
+                        unsigned long long* word, hipStream_t st);
+hipError_t launch_wpred_eval(const pred::Program* prog, const WModel& M, int compact, const void* in, u64 n,
+                             uint8_t* out, hipStream_t st);
 // rmc_check_states on the wide layout: out[t] = the invariant result of M.inv_mask on in[t], by
 // wcheck_invariants with one thread per state (wave = 0: the BFS's and k_wsimulate's check), or by
 // w_check_invariants_wave with one wave per state on a copy in LDS (k_wsimulate_w's)

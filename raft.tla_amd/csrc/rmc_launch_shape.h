@@ -5,6 +5,7 @@
 
 #include "rmc_dev_expand.h"
 #include "rmc_dev_graph.h"
+#include "rmc_dev_pred.h"
 #include "rmc_dev_sharded.h"
 #include "rmc_dev_tools.h"
 #include "rmc_dev_verify.h"
@@ -41,6 +42,25 @@ static hipError_t launch_violations_t(const Params& P, const DevBufs& B, u64 nlo
     const u64 blocks = (nhi - nlo + 255) / 256;
     hipLaunchKernelGGL((k_violations<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, P, B,
                        nlo, nhi, viol);
+    return hipGetLastError();
+}
+
+// The predicate pass of one expansion launch (or of the seed step) over the states it added.
+template <int S, int K>
+static hipError_t launch_pred_t(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi,
+                                unsigned long long* word, hipStream_t st) {
+    if (nhi <= nlo) return hipSuccess;
+    const u64 blocks = (nhi - nlo + kPredThreads - 1) / kPredThreads;
+    hipLaunchKernelGGL((k_pred<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kPredThreads), 0, st, prog,
+                       B, nlo, nhi, word);
+    return hipGetLastError();
+}
+
+template <int S, int K>
+static hipError_t launch_pred_eval_t(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL((k_pred_eval<S, K>), dim3((unsigned)((n + kPredThreads - 1) / kPredThreads)), dim3(kPredThreads),
+                       0, st, prog, in, n, out);
     return hipGetLastError();
 }
 
@@ -245,6 +265,8 @@ static ShapeKernels shape_table() {
     k.cover = launch_cover_t<S, K>;
     k.violations = launch_violations_t<S, K>;
     k.check = launch_check_t<S, K>;
+    k.pred = launch_pred_t<S, K>;
+    k.pred_eval = launch_pred_eval_t<S, K>;
     k.keys = launch_keys_t<S, K>;
     k.set_salt = set_object_salt;
     k.graph_count = [](const Params& P, const DevBufs& B, u64 lo, u64 hi, u32* cnt, hipStream_t st) {

@@ -434,6 +434,28 @@ int main(int argc, char** argv) {
     if (cfg.empty()) cfg = (tla.size() > 4 && tla.substr(tla.size() - 4) == ".tla" ? tla.substr(0, tla.size() - 4) : tla) + ".cfg";
     printf("rmc-tlc: %s\n", rmc_version());
     if (const char* b = getenv("RMC_BUILTIN_RAFT")) if (b[0] == '1') fopts |= RMC_FRONT_BUILTIN_RAFT;
+    // INVARIANTs of the model's own (none of the ten compiled-in ones) are compiled to the
+    // predicate interpreter's bytecode and checked by a pass of the single-GPU search
+    fopts |= RMC_FRONT_PREDICATES;
+    if (depth > 0 && !simulate) fopts |= RMC_FRONT_DEPTH_BOUNDED;
+    rmc_predicates* preds = nullptr;
+    {
+        char perr[2048];
+        if (rmc_predicates_from_files(cfg.c_str(), tla.c_str(), raft.empty() ? nullptr : raft.c_str(),
+                                      fopts | (simulate ? RMC_FRONT_SIMULATE : 0u), &preds, perr, sizeof perr)) {
+            printf("Error: %s\n", perr);
+            return 1;
+        }
+    }
+    const int npred = rmc_predicates_count(preds);
+    if (npred && (cont || gpus > 1 || simulate || !ckpt.empty() || !recover.empty())) {
+        printf("Error: INVARIANT %s is defined by the model and checked by the single-GPU search's predicate pass: "
+               "not with %s\n", rmc_predicates_name(preds, 0),
+               cont ? "-continue" : gpus > 1 ? "-gpus N > 1" : simulate ? "-simulate" : !ckpt.empty() ? "-checkpoint"
+                                                                                                     : "-recover");
+        rmc_predicates_free(preds);
+        return 1;
+    }
     if (simulate) return run_simulation(cfg, tla, raft, fopts, device, depth, num, seed);
     rmc_config c;
     char info[2048];
@@ -468,7 +490,9 @@ int main(int argc, char** argv) {
     }
     // the graph's slot -> state index takes as much HBM as the set: not beside an auto-sized one
     if (!dump.empty() && !capacity && !fpmem) c.state_capacity = 1ull << 26;
-    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 && !(wide && (verify || cont)))
+    // (nor with model-defined invariants, whose pass reads them too)
+    if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 &&
+        !(wide && (verify || cont || npred)))
         c.flags |= RMC_FLAG_SPILL;
     c.device_window = window;
     c.set_bytes = fpmem;
@@ -484,6 +508,16 @@ int main(int argc, char** argv) {
     rmc_ctx* ctx = nullptr;
     rc = rmc_create(&c, &ctx);
     if (rc) { printf("Error: rmc_create failed (%d)\n", rc); return 1; }
+    if (npred) {
+        if (rmc_set_predicates(ctx, preds)) {
+            printf("Error: %s\n", rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 1;
+        }
+        printf("Compiled model-defined invariants:");
+        for (int p = 0; p < npred; ++p) printf("%s %s", p ? "," : "", rmc_predicates_name(preds, p));
+        printf("\n");
+    }
     // -gpus N: one ctx per GPU (devices device..device+N-1), each a rank of the
     // sharded search on librmc's RCCL communicator, each driven by its own
     // thread through every collective (the BFS and the trace walk).  All
@@ -620,7 +654,15 @@ int main(int argc, char** argv) {
         }
         exitcode = 12;
     } else if (r.violated_inv || r.deadlock) {
-        if (r.violated_inv) printf("Error: Invariant %s is violated.\n", inv_name(r.violated_inv));
+        if ((uint32_t)r.violated_inv >= RMC_INV_USER0) {  // a model-defined invariant: bit 16 + p
+            const char* name = rmc_predicates_name(preds, __builtin_ctz((uint32_t)r.violated_inv) - 16);
+            if (rmc_predicate_error(ctx))
+                printf("Error: Evaluating invariant %s failed: a read outside its domain (log[i][n] beyond "
+                       "Len(log[i]), a server index that is Nil, or a field of another message type).\n",
+                       name ? name : "?");
+            else
+                printf("Error: Invariant %s is violated.\n", name ? name : "?");
+        } else if (r.violated_inv) printf("Error: Invariant %s is violated.\n", inv_name(r.violated_inv));
         else printf("Error: Deadlock reached.\n");
         print_behaviour();
         exitcode = 12;
@@ -677,5 +719,6 @@ int main(int argc, char** argv) {
     else
         printf("Finished in %.0fms after recovery (counts include the checkpointed levels)\n", r.seconds * 1e3);
     rmc_destroy(ctx);
+    rmc_predicates_free(preds);
     return exitcode;
 }

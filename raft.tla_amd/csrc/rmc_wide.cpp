@@ -237,6 +237,9 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool cont = continue_on(c);  // (validate_wide refuses it with the ring)
     if (cont)
         if (int rc = viol_begin(c)) return rc;
+    const bool preds = pred_on(c);  // (rmc_set_predicates refuses the ring)
+    if (preds)
+        if (int rc = pred_begin(c)) return rc;
     // Init in the record the seed kernel reads: the work record (= the store's without the ring)
     HIPCHK(c, with_record(B.window ? B.work : B.compact, [&](auto* r) {
         std::remove_pointer_t<decltype(r)> init;
@@ -251,6 +254,10 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         HIPCHK(c, launch_wcover(c->WM, B, 0, 0, 0, c->h_ctr->count, 1, c->d_cov, c->st));
     if (cont)  // the seed's states
         HIPCHK(c, launch_wviolations(c->WM, B, 0, c->h_ctr->count, c->d_viol, c->st));
+    if (preds) {  // the seed's states: a predicate Init fails is the target, at depth 1
+        if (int rc = pred_pass(c, 0, c->h_ctr->count)) return rc;
+        if (int rc = pred_scan(c, 1)) return rc;
+    }
     const u64 CHUNK = 1ull << 22;
     const u64 bound = wide_new_per_state(c->cfg, B.work);
     u64 records = c->h_ctr->count;  // ring: records written so far
@@ -309,7 +316,7 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 c->res.spilled = records > B.window ? records - B.window : 0;
                 c->res.spills = records / B.window;  // passes of the ring
             }
-            if (cover || cont) {
+            if (cover || cont || preds) {
                 // the coverage pass of this launch: the ring still holds its parents [a, b)
                 // (its room is relative to a), and the states it added, [count before, count
                 // after), have their links even on the unstored last level; the violation
@@ -321,6 +328,8 @@ int run_bfs_wide(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 if (cover)
                     HIPCHK(c, launch_wcover(c->WM, B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
                 if (cont) HIPCHK(c, launch_wviolations(c->WM, B, cov_before, c->h_ctr->count, c->d_viol, c->st));
+                if (preds)  // (the predicate pass: those states' records too)
+                    if (int rc = pred_pass(c, cov_before, c->h_ctr->count)) return rc;
             }
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
@@ -472,6 +481,32 @@ int check_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint32_t mask
     HIPCHK(c, hipMemcpy(v.data(), d_out.get(), n * sizeof(int), hipMemcpyDeviceToHost));
     for (size_t t = 0; t < n; ++t) violated[t] = v[t] ? 1 << (v[t] - 1) : 0;
     return 0;
+}
+
+// rmc_eval_predicates on the wide layout: the views as records of the store's kind (the
+// interpreter reads the record the BFS pass reads), through k_wpred_eval into d_out.
+int pred_eval_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint8_t* d_out) {
+    return with_record(c->WB.compact, [&](auto* r) -> int {
+        typedef std::remove_pointer_t<decltype(r)> Rec;
+        std::vector<Rec> in(n);
+        std::string why;
+        for (size_t t = 0; t < n; ++t) {
+            WState s;
+            if (encode_wide(c->WM.S, states[t], &s, &why))
+                return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": " + why);
+            if (wnarrow_bits<Rec>(s))
+                return fail(c, RMC_E_INVAL, "state " + std::to_string(t) + ": beyond the ctx's store record (" +
+                                                std::to_string(Rec::kLW) + " log entries, " + std::to_string(Rec::kKW) +
+                                                " messages)");
+            wconvert(in[t], s);
+        }
+        DevScratch<Rec> d_in;
+        HIPCHK(c, d_in.alloc(n));
+        HIPCHK(c, hipMemcpy(d_in.get(), in.data(), n * sizeof(Rec), hipMemcpyHostToDevice));
+        HIPCHK(c, launch_wpred_eval(c->d_prog, c->WM, c->WB.compact, d_in.get(), (u64)n, d_out, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        return 0;
+    });
 }
 
 int sim_wide(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_beh, std::vector<rmc_state_view>* rec) {

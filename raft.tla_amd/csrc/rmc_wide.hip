@@ -11,6 +11,7 @@
 
 #include "raft_wide.h"
 #include "rmc_cover.h"
+#include "rmc_dev_pred.h"
 #include "rmc_internal.h"
 #include "rmc_viol.h"
 
@@ -393,6 +394,45 @@ __global__ __launch_bounds__(256) void k_wviolations(const WModel M, const WideB
         const u32 v = s_row[threadIdx.x];
         if (v) atomicAdd(&viol[threadIdx.x], (unsigned long long)v);
     }
+}
+
+// Model-defined invariants (rmc_pred.h, rmc_dev_pred.h: the packed k_pred's and k_pred_eval's
+// twins): the BFS pass over the states one launch (or the seed) added, [nlo, nhi), on the
+// store's record in place — the resident store only — and the same interpreter on staged
+// records of the store's kind.  The program in LDS, each thread's stack and bound names an
+// LDS column, as there.
+template <class Store>
+__global__ __launch_bounds__(kPredThreads) void k_wpred(const pred::Program* prog, const WModel M, const WideBufs B,
+                                                        u64 nlo, u64 nhi, unsigned long long* word) {
+    __shared__ PredLds L;
+    pred_load(L, prog);
+    const int n_pred = prog->n_pred;
+    const Store* store = static_cast<const Store*>(B.store);
+    u64 best = ~0ull;
+    nhi = nhi < B.cap ? nhi : B.cap;  // (a launch that overflowed the store is an error: the word is not read)
+    for (u64 i = nlo + (u64)blockIdx.x * kPredThreads + threadIdx.x; i < nhi; i += (u64)gridDim.x * kPredThreads) {
+        const pred::WideAcc<Store> a{store + i, M.S};
+        const int f = pred::first_failing<kPredThreads>(L.entry, n_pred, L.code, a, L.mem + threadIdx.x);
+        if (f) {
+            best = (i << 8) | (u64)(f - 1);
+            break;
+        }
+    }
+    best = pred_wave_min(best);
+    if (__lane_id() == 0 && best != ~0ull) atomicMin(word, (unsigned long long)best);
+}
+
+template <class Store>
+__global__ __launch_bounds__(kPredThreads) void k_wpred_eval(const pred::Program* prog, const WModel M,
+                                                             const Store* in, u64 n, uint8_t* out) {
+    __shared__ PredLds L;
+    pred_load(L, prog);
+    const int n_pred = prog->n_pred;
+    const u64 t = (u64)blockIdx.x * kPredThreads + threadIdx.x;
+    if (t >= n) return;
+    const pred::WideAcc<Store> a{in + t, M.S};
+    for (int p = 0; p < n_pred; ++p)
+        out[t * (u64)n_pred + p] = (uint8_t)pred::run<kPredThreads>(L.code, L.entry[p], a, L.mem + threadIdx.x);
 }
 
 // Every enabled lane of n given states, without dedup (rmc_expand).  Sym: the
@@ -860,6 +900,28 @@ hipError_t launch_wviolations(const WModel& M, const WideBufs& B, u64 nlo, u64 n
     if (B.compact == 2) hipLaunchKernelGGL(k_wviolations<WStateD>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
     else if (B.compact) hipLaunchKernelGGL(k_wviolations<WStateC>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
     else hipLaunchKernelGGL(k_wviolations<WState>, grid, dim3(256), 0, st, M, B, nlo, nhi, viol);
+    return hipGetLastError();
+}
+hipError_t launch_wpred(const pred::Program* prog, const WModel& M, const WideBufs& B, u64 nlo, u64 nhi,
+                        unsigned long long* word, hipStream_t st) {
+    if (nhi <= nlo) return hipSuccess;
+    if (B.window) return hipErrorInvalidValue;  // the resident store only
+    const dim3 grid(grid_for(nhi - nlo, kPredThreads, 4096)), block(kPredThreads);
+    if (B.compact == 2) hipLaunchKernelGGL(k_wpred<WStateD>, grid, block, 0, st, prog, M, B, nlo, nhi, word);
+    else if (B.compact) hipLaunchKernelGGL(k_wpred<WStateC>, grid, block, 0, st, prog, M, B, nlo, nhi, word);
+    else hipLaunchKernelGGL(k_wpred<WState>, grid, block, 0, st, prog, M, B, nlo, nhi, word);
+    return hipGetLastError();
+}
+hipError_t launch_wpred_eval(const pred::Program* prog, const WModel& M, int compact, const void* in, u64 n,
+                             uint8_t* out, hipStream_t st) {
+    if (!n) return hipSuccess;
+    const dim3 grid(grid_for(n, kPredThreads, 1u << 22)), block(kPredThreads);
+    if (compact == 2)
+        hipLaunchKernelGGL(k_wpred_eval<WStateD>, grid, block, 0, st, prog, M, static_cast<const WStateD*>(in), n, out);
+    else if (compact)
+        hipLaunchKernelGGL(k_wpred_eval<WStateC>, grid, block, 0, st, prog, M, static_cast<const WStateC*>(in), n, out);
+    else
+        hipLaunchKernelGGL(k_wpred_eval<WState>, grid, block, 0, st, prog, M, static_cast<const WState*>(in), n, out);
     return hipGetLastError();
 }
 hipError_t launch_wlist(const WModel& M, const WState* in, u64 n, WSucc* out, u64 cap, unsigned long long* count,

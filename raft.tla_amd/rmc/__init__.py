@@ -31,7 +31,10 @@ INV_NAMES = {INV_TYPEOK: "TypeOK", INV_ONE_LEADER: "OneLeaderPerTerm",
              INV_LEADER_VOTES: "LeaderVotesQuorum", INV_CAND_TERM: "CandidateTermNotInLog",
              INV_VOTES_GRANTED: "VotesGrantedInv", INV_QUORUM_LOG: "QuorumLogInv",
              INV_MORE_UP_TO_DATE: "MoreUpToDateCorrect", INV_LEADER_COMPLETE: "LeaderCompleteness"}
-FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED = 1, 2, 4
+FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED, FRONT_PREDICATES = 1, 2, 4, 8
+MAX_PREDICATES = 8       # RMC_MAX_PREDICATES: model-defined invariants per program
+INV_USER0 = 1 << 16      # RMC_INV_USER0: predicate p is bit 16 + p of Result.violated_inv
+PRED_HOLDS, PRED_VIOLATED, PRED_ERROR = 0, 1, 2  # verdicts of rmc_eval_predicates
 FLAG_UNBOUNDED_TERM, FLAG_UNBOUNDED_LOG, FLAG_UNBOUNDED_MSGS, FLAG_UNBOUNDED_DUP = 32, 64, 128, 256
 FLAG_COVERAGE = 512
 FLAG_CONTINUE = 2048  # (bit 10 is not assigned)
@@ -156,7 +159,9 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_sim_config_from_files", "rmc_checkpoint", "rmc_recover", "rmc_model_from_files",
            "rmc_action_location", "rmc_smoke_init", "rmc_get_coverage", "rmc_coverage_action",
            "rmc_check_states", "rmc_state_keys", "rmc_get_violations", "rmc_trace_violation",
-           "rmc_get_levels", "rmc_read_states", "rmc_find_states", "rmc_graph_edges")
+           "rmc_get_levels", "rmc_read_states", "rmc_find_states", "rmc_graph_edges",
+           "rmc_predicates_from_files", "rmc_predicates_free", "rmc_predicates_count", "rmc_predicates_name",
+           "rmc_set_predicates", "rmc_eval_predicates", "rmc_predicate_error")
 
 _lib = None
 
@@ -249,6 +254,21 @@ def native():
         lib.rmc_graph_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(Edge), C.c_size_t,
                                         C.POINTER(C.c_size_t)]
         lib.rmc_graph_edges.restype = C.c_int
+        lib.rmc_predicates_from_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                  C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        lib.rmc_predicates_from_files.restype = C.c_int
+        lib.rmc_predicates_free.argtypes = [C.c_void_p]
+        lib.rmc_predicates_free.restype = None
+        lib.rmc_predicates_count.argtypes = [C.c_void_p]
+        lib.rmc_predicates_count.restype = C.c_int
+        lib.rmc_predicates_name.argtypes = [C.c_void_p, C.c_int]
+        lib.rmc_predicates_name.restype = C.c_char_p
+        lib.rmc_set_predicates.argtypes = [C.c_void_p, C.c_void_p]
+        lib.rmc_set_predicates.restype = C.c_int
+        lib.rmc_eval_predicates.argtypes = [C.c_void_p, C.POINTER(StateView), C.c_size_t, C.POINTER(C.c_uint8)]
+        lib.rmc_eval_predicates.restype = C.c_int
+        lib.rmc_predicate_error.argtypes = [C.c_void_p]
+        lib.rmc_predicate_error.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -270,8 +290,55 @@ def make_config(n_servers=3, n_values=2, max_term=2, max_log_len=1, max_msgs=2, 
                   invariants, device, max_depth, state_capacity, 0, device_window, set_bytes)
 
 
+class Predicates:
+    """The model-defined invariants of a model, compiled (rmc_predicates_from_files): the
+    INVARIANTs of its .cfg that are none of the ten compiled-in ones, in cfg order.
+    `names`: their names; predicate p is bit INV_USER0 << p of Result.violated_inv."""
+
+    def __init__(self, cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False):
+        self.lib = native()
+        self.handle = C.c_void_p()
+        err = C.create_string_buffer(4096)
+        opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_DEPTH_BOUNDED if depth_bounded else 0)
+        rc = self.lib.rmc_predicates_from_files(cfg_path.encode(), tla_path.encode() if tla_path else None,
+                                                raft_path.encode() if raft_path else None, opts,
+                                                C.byref(self.handle), err, 4096)
+        if rc:
+            raise RmcError(rc, err.value.decode())
+        self.names = [self.lib.rmc_predicates_name(self.handle, p).decode()
+                      for p in range(self.lib.rmc_predicates_count(self.handle))]
+
+    def __len__(self):
+        return len(self.names)
+
+    def name_of(self, violated_inv):
+        """The name behind a Result.violated_inv user bit (None for a compiled-in bit)."""
+        for p, name in enumerate(self.names):
+            if violated_inv == INV_USER0 << p:
+                return name
+        return None
+
+    def close(self):
+        if self.handle:
+            self.lib.rmc_predicates_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+def load_model(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False, predicates=False):
+    """(Config, provenance notes, Predicates or None): rmc_model_from_files for a BFS model;
+    predicates=True accepts INVARIANTs of the model's own (RMC_FRONT_PREDICATES) and
+    compiles them — hand them to Checker.set_predicates."""
+    cfg, _sc, notes = model_from_files(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded=depth_bounded,
+                                       predicates=predicates)
+    preds = Predicates(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded) if predicates else None
+    return cfg, notes, preds
+
+
 def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, simulate=False,
-                     depth_bounded=False):
+                     depth_bounded=False, predicates=False):
     """rmc_model_from_files: (Config, SimConfig or None, provenance notes).
     Raises RmcError naming the construct when the model is not the compiled-in
     raft.tla (with its recognised bug variant, bounds and invariants).
@@ -281,7 +348,7 @@ def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False
     cfg, sc = Config(), SimConfig()
     info = C.create_string_buffer(4096)
     opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_SIMULATE if simulate else 0) | \
-        (FRONT_DEPTH_BOUNDED if depth_bounded else 0)
+        (FRONT_DEPTH_BOUNDED if depth_bounded else 0) | (FRONT_PREDICATES if predicates else 0)
     rc = lib.rmc_model_from_files(cfg_path.encode(), tla_path.encode() if tla_path else None,
                                   raft_path.encode() if raft_path else None, opts, C.byref(cfg),
                                   C.byref(sc) if simulate else None, info, 4096)
@@ -515,6 +582,34 @@ class Checker:
         same = (C.c_uint8 * len(views))()
         self._check(self.lib.rmc_state_keys(self.ctx, arr, len(views), keys, refs, same))
         return list(keys), list(same)
+
+    # ---- model-defined invariants (rmc.h "model-defined invariants") ----
+    def set_predicates(self, preds):
+        """rmc_set_predicates: run() then checks the compiled predicates (a Predicates) on
+        every stored state; None removes them.  The ctx keeps its own copy."""
+        self._check(self.lib.rmc_set_predicates(self.ctx, preds.handle if preds is not None else None))
+        self._pred_names = list(preds.names) if preds is not None else []
+
+    def eval_predicates(self, views):
+        """rmc_eval_predicates: per view the verdict of every predicate, in order
+        (PRED_HOLDS, PRED_VIOLATED, PRED_ERROR), by the device interpreter.  `views`: a
+        sequence of StateView, or a ctypes array of them (passed as it is)."""
+        arr = views if isinstance(views, C.Array) else (StateView * len(views))(*views)
+        np_ = len(getattr(self, "_pred_names", []))
+        out = (C.c_uint8 * max(1, len(views) * np_))()
+        self._check(self.lib.rmc_eval_predicates(self.ctx, arr, len(views), out))
+        return [tuple(out[t * np_:(t + 1) * np_]) for t in range(len(views))]
+
+    def predicate_name(self, violated_inv):
+        """The name of the predicate behind a Result.violated_inv user bit, else None."""
+        for p, name in enumerate(getattr(self, "_pred_names", [])):
+            if violated_inv == INV_USER0 << p:
+                return name
+        return None
+
+    def predicate_error(self):
+        """rmc_predicate_error: True if the violation run() reported is an evaluation error."""
+        return bool(self.lib.rmc_predicate_error(self.ctx))
 
     # ---- the state graph of the last completed run() (rmc.h "state graph export") ----
     def levels(self):

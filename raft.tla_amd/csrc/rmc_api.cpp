@@ -15,6 +15,7 @@
 
 #include "rmc_cover.h"
 #include "rmc_ctx.h"
+#include "rmc_units.h"
 #include "rmc_viol.h"
 
 using namespace rmc;
@@ -367,13 +368,15 @@ int rmc_create(const rmc_config* cfg, rmc_ctx** out) {
     const u64 cap = plan.cap, slots = plan.slots, win = plan.window, link_cap = plan.link_cap;
     c->table_slots = slots;
     c->B.cap = win;
+    c->B.lim = win;  // (set again by every launch of rmc_run_bfs)
+    c->B.admit_reserve = 0;
     c->B.tmask = slots - 1;
     c->B.wmask = dev_links ? win - 1 : ~0ull;
     if (hipMalloc(&c->B.store, win * (u64)c->NW * 4) != hipSuccess ||
         hipMalloc(&c->B.parent, link_cap * 8) != hipSuccess || hipMalloc(&c->B.act, link_cap) != hipSuccess ||
         hipMalloc(&c->B.foot, win * 8) != hipSuccess || hipMalloc(&c->B.cls, win) != hipSuccess ||
         hipMalloc(&c->B.table, slots * 8) != hipSuccess || hipMalloc(&c->B.ctr, sizeof(Counters)) != hipSuccess ||
-        hipMalloc(&c->B.word, (1ull << kMaxLaunchLog2) * 2) != hipSuccess ||  // presorted windows of one launch
+        hipMalloc(&c->B.word, std::min<u64>(1ull << kMaxLaunchLog2, win) * 2) != hipSuccess ||  // presorted windows of one launch
         hipMalloc(&c->d_staged, (size_t)c->NW * 4 * 64) != hipSuccess) {
         c->err = "device allocation failed (capacity " + std::to_string(win) + " states)";
         return bail(RMC_E_NOMEM);
@@ -533,9 +536,9 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     } else if (int rc = start_run(c, &depth)) {
         return rc;
     }
-    // states per expansion launch: at most kMaxLaunch (B.word holds one launch's
-    // presorted positions), and a level is cut into EQUAL launches, so no launch
-    // is a small remainder that leaves most of the resident grid idle
+    // states per expansion launch: at most 2^kMaxLaunchLog2 (B.word holds one launch's
+    // presorted positions), so a level is one launch, or beyond that cut into EQUAL
+    // launches: no launch is a small remainder that leaves most of the resident grid idle
     // (RMC_LAUNCH_LOG2: a smaller cap, A/B)
     static const u64 CHUNK = [] {
         const char* e = getenv("RMC_LAUNCH_LOG2");
@@ -564,6 +567,12 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         const u64 even = (hi - lo + nlaunch - 1) / nlaunch;  // <= chunk
         for (u64 a = lo, b = 0; a < hi; a = b) {
             b = std::min(hi, a + even);
+            // the ring's device-side admission (rmc_plan.h): a launch the bound would cut is
+            // launched whole when its reserve fits, and launched again from where it stopped
+            const bool ring = c->spill.on && c->spill.dev_links;
+            bool admit = false, abort_level = false;
+            u64 live_lo = a, reserve = 0, units = 0;
+            ShapeKernels::AdmitShape as{};
             if (c->spill.on) {
                 // a state yields at most `bound` new states; verification parks
                 // every hit of a launch on a spilled owner in hbuf
@@ -574,6 +583,15 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     // the ring window: nothing is ever moved (rmc_plan.h ring_room)
                     const u64 win = c->spill.win;
                     want = std::min(want, ring_room(count, a, win) / bound);
+                    if (want < b - a && !c->sh.verify && !c->sh.sym) {  // (the dynamic-unit kernel's searches)
+                        as = c->k->admit_shape(b - a);
+                        units = rmc_units::units_total(b - a, as.wt, as.ut);
+                        reserve = admit_needs_reserve(c->B.cap, a, win)
+                                      ? admit_reserve(as.grid * 4, units, unit_states(as.wt, as.ut), bound, as.list_cap)
+                                      : 0;
+                        admit = reserve <= kAdmitReserveMax &&
+                                admit_fits(count, admit_stop(launch_store_limit(c->B.cap, true, a, win), reserve));
+                    }
                     if (c->sh.verify && want) {
                         // the launch may overwrite the ring slots of states below
                         // count + n * bound - win (<= a): copy them to the host first, and
@@ -596,57 +614,87 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     want = std::min(want, (c->B.cap - count) / bound);
                     if (c->sh.verify) c->B.vlo = c->spill.base;  // [0, base) were copied to the host by spill_to
                 }
-                if (want == 0) return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
-                b = a + want;
-            }
-            // coverage reads Counters.count back after every launch, so it is current here
-            const u64 cov_before = c->h_ctr->count;
-            HIPCHK(c, c->k->expand(c->sh.sym, c->sh.verify, c->P, c->PT, c->B, a, b, c->st));
-            c->res.expand_launches += 1;
-            if (c->sh.sym && !c->sh.verify) {
-                HIPCHK(c, c->k->ties(c->P, c->PT, c->B, c->st));
-                HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
-            }
-            if (c->sh.verify) {
-                const u64 before = c->h_ctr->count;
-                if (int rc = read_counters(c)) return rc;
-                if (c->h_ctr->overflow) break;
-                HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, before, c->h_ctr->count, c->st));
-                HIPCHK(c, c->k->verify(c->sh.sym, c->P, c->PT, c->B, c->h_ctr->vcount, c->st));
-                HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
-                c->h_ctr->vcount = 0;
-                if (c->h_ctr->hcount)  // hits on spilled owners: against their host copies
-                    if (int rc = verify_host_hits(c, c->h_ctr->hcount)) return rc;
-            }
-            if (c->spill.on) {
-                if (int rc = read_counters(c)) return rc;
-                if (c->h_ctr->overflow || c->h_ctr->table_full) break;
-                if (c->h_ctr->count > c->spill.total_cap)
-                    return fail(c, RMC_E_CAPACITY, "spill: more states than rmc_config.state_capacity (" +
-                                                       std::to_string(c->spill.total_cap) + ")");
-                if (c->spill.dev_links) {  // the ring: states below count - win are overwritten
-                    const u64 cnt = c->h_ctr->count, win = c->spill.win;
-                    c->spill.base = cnt > win ? cnt - win : 0;
-                    c->res.spilled = c->spill.base;
-                    c->res.spills = cnt / win;  // passes of the ring
+                // the reserve does not fit (or no admission in this search): sized by the bound
+                if (!admit) {
+                    if (want == 0) return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
+                    b = a + want;
                 }
             }
-            if (cover || cont || preds) {
-                // the coverage pass of this launch: its parents [a, b) are still resident
-                // (the store; the linear window, which moves only [base, a) and before the
-                // launch; the ring, whose room is relative to a), and the states it added
-                // are [count before, count after) — after k_ties, Publish / Verify.  The
-                // violation pass and the predicate pass read those states: resident too
-                // (ring_room keeps a launch's new states inside the window)
-                if (!c->sh.verify && !c->spill.on) {  // (those paths have read the counters)
+            for (bool resumed = false;; resumed = true) {
+                c->B.lim = launch_store_limit(c->B.cap, ring, live_lo, c->spill.win);
+                c->B.admit_reserve = admit ? (u32)reserve : 0u;
+                // coverage reads Counters.count back after every launch, so it is current here
+                const u64 cov_before = c->h_ctr->count;
+                if (resumed) {
+                    HIPCHK(c, c->k->expand_resume(c->P, c->PT, c->B, a, b, c->st));
+                } else {
+                    HIPCHK(c, c->k->expand(c->sh.sym, c->sh.verify, c->P, c->PT, c->B, a, b, c->st));
+                }
+                c->res.expand_launches += 1;
+                if (c->sh.sym && !c->sh.verify) {
+                    HIPCHK(c, c->k->ties(c->P, c->PT, c->B, c->st));
+                    HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
+                }
+                if (c->sh.verify) {
+                    const u64 before = c->h_ctr->count;
                     if (int rc = read_counters(c)) return rc;
-                    if (c->h_ctr->overflow || c->h_ctr->table_full) break;
+                    if (c->h_ctr->overflow) { abort_level = true; break; }
+                    HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, before, c->h_ctr->count, c->st));
+                    HIPCHK(c, c->k->verify(c->sh.sym, c->P, c->PT, c->B, c->h_ctr->vcount, c->st));
+                    HIPCHK(c, hipMemsetAsync(&c->B.ctr->vcount, 0, 8, c->st));
+                    c->h_ctr->vcount = 0;
+                    if (c->h_ctr->hcount)  // hits on spilled owners: against their host copies
+                        if (int rc = verify_host_hits(c, c->h_ctr->hcount)) return rc;
                 }
-                if (cover) HIPCHK(c, c->k->cover(c->P, c->B, a, b, cov_before, c->h_ctr->count, 0, c->d_cov, c->st));
-                if (cont) HIPCHK(c, c->k->violations(c->P, c->B, cov_before, c->h_ctr->count, c->d_viol, c->st));
-                if (preds)
-                    if (int rc = pred_pass(c, cov_before, c->h_ctr->count)) return rc;
+                if (c->spill.on) {
+                    if (int rc = read_counters(c)) return rc;
+                    if (c->h_ctr->overflow || c->h_ctr->table_full) { abort_level = true; break; }
+                    if (c->h_ctr->count > c->spill.total_cap)
+                        return fail(c, RMC_E_CAPACITY, "spill: more states than rmc_config.state_capacity (" +
+                                                           std::to_string(c->spill.total_cap) + ")");
+                    if (c->spill.dev_links) {  // the ring: states below count - win are overwritten
+                        const u64 cnt = c->h_ctr->count, win = c->spill.win;
+                        c->spill.base = cnt > win ? cnt - win : 0;
+                        c->res.spilled = c->spill.base;
+                        c->res.spills = cnt / win;  // passes of the ring
+                    }
+                }
+                if (cover || cont || preds) {
+                    // the coverage pass of this launch: its parents [a, b) are still resident
+                    // (the store; the linear window, which moves only [base, a) and before the
+                    // launch; the ring, whose room is relative to a: a launch stopped on
+                    // admission tallies all its parents here, its re-launches none), and the
+                    // states it added are [count before, count after) — after k_ties, Publish / Verify.  The
+                    // violation pass and the predicate pass read those states: resident too
+                    // (ring_room keeps a launch's new states inside the window)
+                    if (!c->sh.verify && !c->spill.on) {  // (those paths have read the counters)
+                        if (int rc = read_counters(c)) return rc;
+                        if (c->h_ctr->overflow || c->h_ctr->table_full) { abort_level = true; break; }
+                    }
+                    if (cover)
+                        HIPCHK(c, c->k->cover(c->P, c->B, resumed ? b : a, b, cov_before, c->h_ctr->count, 0, c->d_cov,
+                                              c->st));
+                    if (cont) HIPCHK(c, c->k->violations(c->P, c->B, cov_before, c->h_ctr->count, c->d_viol, c->st));
+                    if (preds)
+                        if (int rc = pred_pass(c, cov_before, c->h_ctr->count)) return rc;
+                }
+                // a launch that stopped on admission left units unclaimed (every claimed one is
+                // finished): again over [a, b), live from the first window not fully claimed
+                const u64 claimed = rmc_units::units_claimed(c->h_ctr->wnext);
+                if (!admit || claimed >= units) break;
+                live_lo = admit_live_lo(a, b - a, claimed, as.wt, 4ull * rmc_units::unit_groups(as.wt, as.ut));
+                reserve = admit_needs_reserve(c->B.cap, live_lo, c->spill.win)
+                              ? admit_reserve(as.grid * 4, units - claimed, unit_states(as.wt, as.ut),
+                                              max_new_per_state(c), as.list_cap)
+                              : 0;
+                if (!admit_fits(c->h_ctr->count,
+                                admit_stop(launch_store_limit(c->B.cap, true, live_lo, c->spill.win), reserve)))
+                    return window_too_small(c, c->spill.win, slot_bytes(c->sh.verify));
+                // the work counter without its stop bit and the count of the waves that left
+                c->h_ctr->wnext = claimed;
+                HIPCHK(c, hipMemcpyAsync(&c->B.ctr->wnext, &c->h_ctr->wnext, 8, hipMemcpyHostToDevice, c->st));
             }
+            if (abort_level) break;
         }
         if (int rc = end_level(c, hi, &depth, cb, user, t0, text, &more)) return rc;
     }

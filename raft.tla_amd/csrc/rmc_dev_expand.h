@@ -74,7 +74,7 @@ __device__ __forceinline__ void flush_list(const Params& P, const DevBufs& B, u6
     if constexpr (C::REP) flush_new<S, K, true>(P, B, lo, l_rel, l_lane, n);
     else if constexpr (C::POOL) flush_pool<S, K>(P, B, lo, l_rel, l_lane, l_dest, n);
     else if constexpr (C::DIST) flush_dist<S, K>(P, B, lo, l_rel, l_lane, l_dest, l_key, l_ks, n);
-    else flush_new<S, K>(P, B, lo, l_rel, l_lane, n);
+    else flush_new<S, K, false, C::DYN != 0>(P, B, lo, l_rel, l_lane, n);  // dynamic units: admission
 }
 
 template <int S, int K, class C>
@@ -163,8 +163,19 @@ __device__ __forceinline__ void expand_body(const Params& P, const PermTable& PT
     u64 win = DYN ? 0ull : (u64)blockIdx.x * 256ull * wt;
     for (;; win += (u64)gridDim.x * 256ull * wt) {  // block-uniform (DYN: wave-uniform)
     if constexpr (DYN != 0) {
+        // admission (rmc_plan.h): a flush that takes the count within B.admit_reserve of
+        // B.lim raises rmc_units::kStopBit in the work counter (flush_new), and a claim that
+        // returns it names no unit (it decodes to win >= nf below), so the wave leaves as at the launch's
+        // end; a claimed unit is always finished.  The wave takes its count back — the low
+        // half stays the units claimed, the high half counts the waves that left — so the
+        // host re-launches from exactly there.  Nothing is read on the claim path: a
+        // device-scope load of the count before every claim measured +43 % on MCraftBench
+        // (profiles/r16/level_launch/claim_variants.txt)
         u32 unit = 0;
-        if (me == 0) unit = (u32)atomicAdd((unsigned long long*)&B.ctr->wnext, 1ull);
+        if (me == 0) {
+            unit = (u32)atomicAdd((unsigned long long*)&B.ctr->wnext, 1ull);
+            if (unit & rmc_units::kStopBit) atomicAdd((unsigned long long*)&B.ctr->wnext, 0xFFFFFFFFull);
+        }
         if constexpr (GROUPS) {
             // decoded by lane 0 before the broadcast: the division's temporaries are
             // vector registers, free between two units, not scalars held over the walk

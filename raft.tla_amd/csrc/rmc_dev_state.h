@@ -7,6 +7,7 @@
 #include "raft_packed.h"
 #include "rmc_dev_set.h"
 #include "rmc_internal.h"
+#include "rmc_units.h"
 
 namespace rmc {
 
@@ -91,7 +92,7 @@ __device__ __forceinline__ void commit_new(int is_new, const u64 (&w)[S], const 
     base = bcast64(base, leader);
     if (!is_new) return;
     const u64 ni = base + (u64)__popcll(bal & ((1ull << me) - 1ull));
-    if (ni >= B.cap) {
+    if (ni >= B.lim) {
         atomicOr(&B.ctr->overflow, 1u);
         return;
     }
@@ -127,7 +128,7 @@ struct RepRec {
 // runs it together, so the rare new-state path does not serialise the
 // per-lane expansion loop.  REP: the parents are replicated-level records
 // (B.rep), their refs global.
-template <int S, int K, bool REP = false>
+template <int S, int K, bool REP = false, bool ADMIT = false>
 __device__ __forceinline__ void flush_new(const Params& P, const DevBufs& B, u64 lo, const u32* l_rel,
                                           const uint8_t* l_lane, u32 n) {
     constexpr int NW = 2 * S + K;
@@ -135,13 +136,20 @@ __device__ __forceinline__ void flush_new(const Params& P, const DevBufs& B, u64
     wave_sync_lds();
     const int me = (int)__lane_id();
     u64 base = 0;
-    if (me == 0) base = atomicAdd((unsigned long long*)&B.ctr->count, (unsigned long long)n);
+    if (me == 0) {
+        base = atomicAdd((unsigned long long*)&B.ctr->count, (unsigned long long)n);
+        // ADMIT: the count is past the launch's admission stop — no further unit is claimed
+        // (expand_body).  Lane 0 issues this before its wave's next claim, on the same word.
+        if constexpr (ADMIT)
+            if (base + n + B.admit_reserve > B.lim)
+                atomicOr((unsigned long long*)&B.ctr->wnext, (unsigned long long)rmc_units::kStopBit);
+    }
     base = bcast64(base, 0);
     for (u32 e = (u32)me; e < n; e += 64) {
         const u64 rel = l_rel[e];
         const int lane = l_lane[e];
         const u64 ni = base + e;
-        if (ni >= B.cap) {
+        if (ni >= B.lim) {  // the launch's limit: the capacity, on the ring the live window's end
             atomicOr(&B.ctr->overflow, 1u);
             continue;
         }

@@ -230,7 +230,7 @@ int enqueue_round(rmc_ctx* c, Run& R, u64 k) {
         R.ovf_done += n;
         R.round_kind[b] = 2;
     } else if (R.cursor < R.hi) {
-        const u64 n = round_states(R.hi - R.cursor, c->B.kcap, D.fill, R.rho, R.split_cap, 1ull << kMaxLaunchLog2);
+        const u64 n = round_states(R.hi - R.cursor, c->B.kcap, D.fill, R.rho, R.split_cap, 1ull << kMaxDistLaunchLog2);
         HIPCHK(c, hipEventRecord(S.k0, c->st));
         HIPCHK(c, c->k->expand_dist(c->sh.sym, c->sh.verify, c->P, c->PT, Bb, R.cursor, R.cursor + n, c->st));
         // the pool flush's remote successors: keyed and routed to the outboxes

@@ -92,6 +92,12 @@ struct DevBufs {
     // canonicalised by k_ties after each expansion launch
     u64* ties;
     u64 tie_cap;
+    // per launch (rmc_plan.h): the store index no flush may reach — cap, and on the ring
+    // never past live_lo + window (the overflow bit instead of a live slot overwritten) —
+    // and the reserve of a dynamic-unit launch's admission: once the count is above
+    // lim - admit_reserve no further unit is claimed (0: no admission, lim is the only bound)
+    u64 lim;
+    u32 admit_reserve;
 };
 
 struct PermTable {
@@ -128,6 +134,17 @@ struct ShapeKernels {
     using Range = hipError_t(bool sym, const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi,
                              hipStream_t st);
     Expand *expand, *expand_dist;  // over store[lo, hi): single GPU / sharded (outbox and pool in B)
+    // The plain single-GPU search's launch (k_expand_sort, dynamic units) over nf states: its
+    // blocks, the tiles of its windows and units, and the entries a wave's list holds — what
+    // the ring's admission reserve is made of (rmc_plan.h admit_reserve).
+    struct AdmitShape {
+        u64 grid;
+        u32 wt, ut, list_cap;
+    };
+    AdmitShape (*admit_shape)(u64 nf);
+    // ... re-launched over the same [lo, hi) after it stopped on admission (B.admit_reserve): from
+    // the Counters.wnext it left, on the presorted positions it left in B.word
+    hipError_t (*expand_resume)(const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi, hipStream_t st);
     hipError_t (*expand_rep)(const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi, hipStream_t st);
     hipError_t (*route)(const Params& P, const DevBufs& B, hipStream_t st);  // k_route_fix, then k_route
     hipError_t (*ties)(const Params& P, const PermTable& PT, const DevBufs& B, hipStream_t st);
@@ -203,8 +220,10 @@ static_assert(sizeof(Counters) % 8 == 0, "Counters travel as u64 words");
 hipError_t launch_pack_counts(const DevBufs& B, u64 host_more, u64 ovf_done, u64* out, hipStream_t st,
                               u64* mirror = nullptr);
 // States per single-GPU expansion launch at most (B.word holds one launch's
-// presorted window positions).
-constexpr int kMaxLaunchLog2 = 25;
+// presorted window positions: min(2^kMaxLaunchLog2, the store's states) entries);
+// a launch of the sharded search (rmc_dist.cpp round_states) at most 2^kMaxDistLaunchLog2.
+constexpr int kMaxLaunchLog2 = 28;
+constexpr int kMaxDistLaunchLog2 = 25;
 // Presorted windows: k_window_order over the launch [lo, hi) for an expansion
 // grid of `grid` blocks and windows of at most wt_max tiles (B.word).
 hipError_t launch_window_order(const DevBufs& B, u64 lo, u64 hi, u64 grid, u64 wt_max, hipStream_t st);

@@ -11,6 +11,7 @@
 #include "rmc_dev_outbox.h"
 #include "rmc_dev_set.h"
 #include "rmc_internal.h"
+#include "rmc_plan.h"
 
 namespace rmc {
 
@@ -142,8 +143,7 @@ hipError_t launch_window_order(const DevBufs& B, u64 lo, u64 hi, u64 grid, u64 w
     if (nf == 0) return hipSuccess;
     if (wt_max > 16 || nf > (1ull << kMaxLaunchLog2)) return hipErrorInvalidValue;
     // the expansion kernel's window size for this launch (expand_body: per_block)
-    const u64 per_block = (nf + grid * 256ull - 1) / (grid * 256ull);
-    const u64 wt = per_block < wt_max ? (per_block ? per_block : 1ull) : wt_max;
+    const u64 wt = rmc_host::launch_window_tiles(nf, grid, wt_max);
     const u64 nwin = (nf + 256ull * wt - 1) / (256ull * wt);
     // its own grid: one round of its resident blocks (RMC_WORDER_GRID=0: the expansion's, round 5)
     static const u64 og = [] {

@@ -10,6 +10,7 @@
 #include "rmc_dev_tools.h"
 #include "rmc_dev_verify.h"
 #include "rmc_internal.h"
+#include "rmc_plan.h"
 
 namespace rmc {
 
@@ -81,7 +82,7 @@ static hipError_t launch_keys_t(bool sym, const Params& P, const PermTable& PT, 
     return hipGetLastError();
 }
 
-// Blocks of the expansion kernels (RMC_EXPAND_GRID for A/B runs; default
+// Blocks of the expansion kernels (RMC_EXPAND_GRID for A/B runs, from 1 block; default
 // 1024 = the resident blocks at 4 waves/SIMD: 4 per CU x 256 CUs, so a launch
 // is one block round and every window sorts more tiles; 309.7 vs 315.6 ms per
 // MCraftBench BFS against 2048, profiles/r03/ab/).  The other grid-stride
@@ -90,7 +91,7 @@ static u64 expand_grid_env() {
     static u64 v = [] {
         const char* e = getenv("RMC_EXPAND_GRID");
         const long long x = e ? atoll(e) : 0;
-        return x >= 64 && x <= (1 << 20) ? (u64)x : (u64)0;
+        return x >= 1 && x <= (1 << 20) ? (u64)x : (u64)0;
     }();
     return v;
 }
@@ -119,25 +120,51 @@ static hipError_t launch_n(void (*kernel)(KA...), u64 n, u64 max_blocks, hipStre
 // One expansion launch over [lo, hi): `kernel` on RMC_EXPAND_GRID blocks (not kFixedGrid), else
 // on `dflt` blocks (0: one round of the kernel's resident blocks).  kPresorted: after
 // k_window_order over the same launch and grid.  kCapacity: then a depth-bounded unconstrained
-// model's capacity pass.
-enum : unsigned { kPresorted = 1, kFixedGrid = 2, kCapacity = 4 };
+// model's capacity pass.  kResume: a presorted launch that stopped on admission, launched
+// again: no k_window_order (B.word and Counters.wnext are as it left them) and no second
+// capacity pass.
+enum : unsigned { kPresorted = 1, kFixedGrid = 2, kCapacity = 4, kResume = 8 };
+template <class Kernel>
+static u64 expansion_grid(Kernel kernel, unsigned how, u64 dflt, u64 nf) {
+    const u64 blocks = (nf + 255) / 256;
+    const u64 want = expand_grid_env() && !(how & kFixedGrid) ? expand_grid_env()
+                     : dflt                                   ? dflt
+                                                              : resident_grid(reinterpret_cast<const void*>(kernel));
+    return blocks < want ? blocks : want;
+}
 template <int S, int K, class Kernel>
 static hipError_t expansion(Kernel kernel, unsigned how, u64 dflt, const Params& P, const PermTable& PT,
                             const DevBufs& B, u64 lo, u64 hi, hipStream_t st) {
     if (hi == lo) return hipSuccess;
     const u64 blocks = (hi - lo + 255) / 256;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const u64 want = expand_grid_env() && !(how & kFixedGrid) ? expand_grid_env()
-                     : dflt                                   ? dflt
-                                                              : resident_grid(reinterpret_cast<const void*>(kernel));
-    const u64 eg = blocks < want ? blocks : want;
-    if (how & kPresorted)
+    const u64 eg = expansion_grid(kernel, how, dflt, hi - lo);
+    if ((how & kPresorted) && !(how & kResume))
         if (hipError_t e = launch_window_order(B, lo, hi, eg, 16, st)) return e;
     hipLaunchKernelGGL(kernel, dim3((unsigned)eg), dim3(256), 0, st, P, PT, B, lo, hi);
-    if ((how & kCapacity) && P.unbounded)
+    if ((how & kCapacity) && !(how & kResume) && P.unbounded)
         hipLaunchKernelGGL((k_capacity_check<S, K>), dim3((unsigned)(blocks < kStrided ? blocks : kStrided)), dim3(256),
                            0, st, P, B, lo, hi);
     return hipGetLastError();
+}
+
+// The plain single-GPU kernel: 5 probes, 6 waves/SIMD (80 VGPRs).  S >= 4 (68 / 92 lanes): 5
+// waves (96 VGPRs, 16 B of scratch) beat 6 waves with 48 B of spills: MCraft5 -depth 20 206 vs
+// 245-246 ms (4 probes at 6 waves 247-248 ms), profiles/r06/ab/s5_waves.txt
+template <int S, int K>
+static constexpr auto sort_kernel() {
+    return &k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, S >= 4 ? 5 : 6>;
+}
+template <int S, int K>
+static ShapeKernels::AdmitShape admit_shape_t(u64 nf) {
+    typedef ExpandSort<5, K <= 4 ? 1 : 0> C;
+    static_assert(C::DYN != 0 && C::PRESORT, "admission: the dynamic-unit kernel");
+    ShapeKernels::AdmitShape a{};
+    a.grid = nf ? expansion_grid(sort_kernel<S, K>(), kPresorted, 0, nf) : 0;
+    a.wt = a.grid ? (u32)rmc_host::launch_window_tiles(nf, a.grid, (u64)C::WTILES) : 0;
+    a.ut = (u32)C::UNIT_TILES;
+    a.list_cap = (u32)WCAP;
+    return a;
 }
 
 template <int S, int K>
@@ -158,11 +185,7 @@ static hipError_t launch_expand(bool sym, bool verify, const Params& P, const Pe
             return expansion<S, K>(&k_expand_sym<S, K, kBatch, 1>, kPresorted | C, 2048, P, PT, B, lo, hi, st);
     }
     if (verify) return expansion<S, K>(&k_expand<S, K, false, kBatch, false, true>, C, 0, P, PT, B, lo, hi, st);
-    // 5 probes, 6 waves/SIMD (80 VGPRs).  S >= 4 (68 / 92 lanes): 5 waves (96 VGPRs,
-    // 16 B of scratch) beat 6 waves with 48 B of spills: MCraft5 -depth 20 206 vs
-    // 245-246 ms (4 probes at 6 waves 247-248 ms), profiles/r06/ab/s5_waves.txt
-    return expansion<S, K>(&k_expand_sort<S, K, 5, K <= 4 ? 1 : 0, S >= 4 ? 5 : 6>, kPresorted | C, 0, P, PT, B, lo, hi,
-                           st);
+    return expansion<S, K>(sort_kernel<S, K>(), kPresorted | C, 0, P, PT, B, lo, hi, st);
 }
 
 template <int S, int K>
@@ -208,6 +231,11 @@ static ShapeKernels shape_table() {
     ShapeKernels k{};
     k.expand = launch_expand<S, K>;
     k.expand_dist = launch_expand_dist<S, K>;
+    k.admit_shape = admit_shape_t<S, K>;
+    k.expand_resume = [](const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi, hipStream_t st) {
+        if (P.symmetry) return hipErrorInvalidValue;  // the plain search only
+        return expansion<S, K>(sort_kernel<S, K>(), kPresorted | kResume, 0, P, PT, B, lo, hi, st);
+    };
     k.expand_rep = [](const Params& P, const PermTable& PT, const DevBufs& B, u64 lo, u64 hi, hipStream_t st) {
         if (hi != lo && P.symmetry) return hipErrorInvalidValue;  // the plain search only
         return expansion<S, K>(&k_expand_dist<S, K, kBatch, true, 4>, 0, 0, P, PT, B, lo, hi, st);

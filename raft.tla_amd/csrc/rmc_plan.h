@@ -65,8 +65,9 @@ inline uint64_t window_bytes_per_state(uint64_t state_words) { return state_word
 // Bytes of a ctx planned this way: the allocations rmc_create sizes from the
 // plan (window, links, set) and the reserve the plan makes for the hit buffers.
 // Not in it, as they were never budgeted: the counters, the launch's presort
-// words, staging, the SYMMETRY tie buffer — and the one 1-GiB hit buffer of a
-// resident verifying ctx, which only the spilled plan reserves; it comes out of
+// words (B.word: 2 B per state of the largest launch, min(2^28, the window) states, so up
+// to 512 MiB where it was 64 MiB), staging, the SYMMETRY tie buffer — and the one 1-GiB
+// hit buffer of a resident verifying ctx, which only the spilled plan reserves; it comes out of
 // the share of free HBM the budget leaves.
 inline uint64_t packed_plan_bytes(const PackedPlanIn& in, const PackedPlan& p) {
     return p.window * window_bytes_per_state(in.state_words) + p.link_cap * kLinkBytes + p.slots * slot_bytes(in.verify) +
@@ -159,5 +160,56 @@ inline uint64_t packed_new_states_bound(uint64_t lanes, uint64_t S, uint64_t V, 
 // built — so a launch of n states, each yielding at most `bound` new ones,
 // overwrites no live state when count + n * bound <= a + win: the states' room.
 inline uint64_t ring_room(uint64_t count, uint64_t a, uint64_t win) { return count - a < win ? a + win - count : 0; }
+
+// ---- device-side admission of a ring launch -----------------------------------------
+// A launch of the dynamic-unit kernel (rmc_units.h) need not be sized by the bound: no
+// unit is claimed once the count is above the stop, live_lo + win - reserve,
+// where live_lo is the oldest state the launch still reads and the reserve is what the
+// launch's waves can add after the count has passed the stop.  The flushes see the count
+// (their allocation returns it); the claims do not read it.  Take the first flush that
+// takes the count above the stop.  From it on every flush raises the stop bit of the
+// work counter (rmc_units.h kStopBit) before its wave's next claim — both are atomics of
+// one lane on one word — so after its first flush from then on a wave claims nothing:
+// it adds what its list carried, at most list_cap entries, and the new states of the
+// unit it is in, at most unit_states * bound.  So the count never passes stop +
+// reserve = live_lo + win, and no state at or above live_lo is overwritten.
+
+// Tiles per window of a presorted launch of nf states on `grid` blocks (expand_body's
+// and k_window_order's wt): wt_max, fewer when every block would not get a full window.
+inline uint64_t launch_window_tiles(uint64_t nf, uint64_t grid, uint64_t wt_max) {
+    const uint64_t per_block = (nf + grid * 256 - 1) / (grid * 256);
+    return per_block < wt_max ? (per_block ? per_block : 1) : wt_max;
+}
+// States of the launch's unit: a wave's 64 positions of at most unit_tiles of a window's wt tiles.
+inline uint64_t unit_states(uint64_t wt, uint64_t unit_tiles) { return std::min(wt, unit_tiles) * 64; }
+// `waves`: the launch's, and never more than the units it has left to claim (a re-launch
+// near the end of its range: a wave without a unit adds nothing, its list starts empty).
+inline uint64_t admit_reserve(uint64_t waves, uint64_t units_left, uint64_t unit_states, uint64_t bound,
+                              uint64_t list_cap) {
+    return std::min(waves, units_left) * (unit_states * bound + list_cap);
+}
+// No reserve is needed where the store's capacity ends before the ring wraps onto live_lo:
+// the store limit alone (a capacity error) keeps every live state.
+inline bool admit_needs_reserve(uint64_t cap, uint64_t live_lo, uint64_t win) { return cap > live_lo + win; }
+// The count above which no unit is claimed, under the launch's store limit `lim`
+// (launch_store_limit below: live_lo + win on the ring); 0: the reserve alone exceeds it.
+// The device holds the reserve in 32 bits (DevBufs.admit_reserve) and compares
+// count + reserve > lim.
+inline uint64_t admit_stop(uint64_t lim, uint64_t reserve) { return lim > reserve ? lim - reserve : 0; }
+constexpr uint64_t kAdmitReserveMax = 0xFFFFFFFFull;
+// The reserve fits: the launch starts below its stop, so its first claims get units.  (The
+// condition under which the device stops claiming, negated: count > admit_stop stops.)
+inline bool admit_fits(uint64_t count, uint64_t stop) { return stop > count; }
+// A launch over [lo, lo + nf) that stopped with wnext units claimed (rmc_units.h
+// units_claimed; each one finished): the first state of the first window not fully claimed — units
+// are claimed window-major, groups_x4 = 4 * unit_groups(wt, ut) per window — which the
+// re-launch takes as its live_lo.
+inline uint64_t admit_live_lo(uint64_t lo, uint64_t nf, uint64_t wnext, uint64_t wt, uint64_t groups_x4) {
+    return lo + std::min(nf, wnext / groups_x4 * 256 * wt);
+}
+// The store index no flush may reach in a launch: the capacity, and on the ring live_lo + win.
+inline uint64_t launch_store_limit(uint64_t cap, bool ring, uint64_t live_lo, uint64_t win) {
+    return ring ? std::min(cap, live_lo + win) : cap;
+}
 
 }  // namespace rmc_host

@@ -49,7 +49,7 @@ void spill_rebase(rmc_ctx* c, u64 base) {
         c->B.act = X.act;
         c->B.foot = X.foot;
         c->B.cls = X.cls;
-        c->B.cap = X.total_cap;
+        c->B.cap = c->B.lim = X.total_cap;
         return;
     }
     const uintptr_t nw = (uintptr_t)c->NW;
@@ -61,6 +61,7 @@ void spill_rebase(rmc_ctx* c, u64 base) {
     c->B.cls = (uint8_t*)((uintptr_t)X.cls - (uintptr_t)base);
     // device links hold total_cap states: no store index may pass it
     c->B.cap = X.dev_links ? std::min(base + X.win, X.total_cap) : base + X.win;
+    c->B.lim = c->B.cap;
 }
 
 // Address space for the trace links of every state the set can hold; pages

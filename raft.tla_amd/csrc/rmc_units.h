@@ -41,6 +41,13 @@ RMC_UNITS_HD inline Unit unit_decode(uint32_t id, uint32_t wt, uint32_t ut, uint
     return u;
 }
 
+// Admission (rmc_plan.h): Counters.wnext carries this bit once a flush has taken the count
+// past the launch's stop; a claim that returns it names no unit (it decodes to a window past
+// any launch: a launch has fewer than 2^24 units) and is taken back, so the bits below it
+// stay the units claimed.
+constexpr uint32_t kStopBit = 0x80000000u;
+RMC_UNITS_HD inline uint64_t units_claimed(uint64_t wnext) { return wnext & (kStopBit - 1u); }
+
 // Units of a launch of nf states: every id below it names a unit of a window
 // that starts inside the launch, every id from it on decodes to win >= nf.
 RMC_UNITS_HD inline uint64_t units_total(uint64_t nf, uint32_t wt, uint32_t ut) {

@@ -539,7 +539,8 @@ int rmc_graph_edges(rmc_ctx* ctx, uint64_t lo, uint64_t hi, rmc_edge* out, size_
 #define RMC_SIM_TRUNCATE 1
 /* TLC's draw (its simulator's action choice, restated): Next's actions — each
  * instance of Restart .. AppendEntries (\E over the constant Server/Value sets
- * expands into one action each), Receive, DuplicateMessage and DropMessage
+ * expands into one action each; the sets are the model's, so ClientRequest has
+ * n_servers * n_values actions), Receive, DuplicateMessage and DropMessage
  * (\E m \in DOMAIN messages ranges over the state) one action each — are
  * visited from a uniformly random index with a random prime stride (primes
  * above the action count, so every action is visited); the first one with a

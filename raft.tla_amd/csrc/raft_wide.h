@@ -786,20 +786,35 @@ RMC_HD u64 range_word(const u64 (&en)[NC], int c, int lo, int hi) {
     if (hi < b0 + 64) m &= (1ull << (hi - b0)) - 1ull;
     return m;
 }
+// The action list is the model's: the lane table always holds VMAX ClientRequest
+// lanes per server, and those with v >= |Value| are never enabled and no action
+// of the model's Next, so they take no index (tlc_action_lane skips them; with
+// |Value| = VMAX the action index is the lane).
+RMC_HD int tlc_actions(const WLanes& L, int V) { return L.off[7] - L.off[1] * (VMAX - V) + 3; }
+// lane of server-family action a (a < tlc_actions - 3)
+RMC_HD int tlc_action_lane(const WLanes& L, int V, int a) {
+    const int o4 = L.off[4], S = L.off[1];
+    if (a < o4) return a;
+    const int k = a - o4;
+    if (k < S * V) return o4 + (k / V) * VMAX + k % V;
+    return a + S * (VMAX - V);
+}
 template <int NC>
-RMC_HD int tlc_draw(const u64 (&en)[NC], int nl, int o7, int o8, int o9, u64& rs) {
+RMC_HD int tlc_draw(const u64 (&en)[NC], const WLanes& L, int V, u64& rs) {
     auto on = [&](int lane) { return ((en[lane >> 6] >> (lane & 63)) & 1ull) != 0; };
-    const int nact = o7 + 3;
+    const int nl = L.off[10], o7 = L.off[7], o8 = L.off[8], o9 = L.off[9];
+    const int nact = tlc_actions(L, V), nsrv = nact - 3;
     const u32 primes[8] = {89, 97, 101, 103, 107, 109, 113, 127};
     const u32 start = (u32)(w_rand(rs) % (u64)nact), stride = primes[w_rand(rs) & 7u];
     const u32 step = stride % (u32)nact;  // (start + i * stride) % nact, one addition per action
     u32 a = start;
     for (int i = 0; i < nact; ++i, a = a + step >= (u32)nact ? a + step - (u32)nact : a + step) {
-        if ((int)a < o7) {
-            if (on((int)a)) return (int)a;
+        if ((int)a < nsrv) {
+            const int lane = tlc_action_lane(L, V, (int)a);
+            if (on(lane)) return lane;
             continue;
         }
-        const int f = (int)a - o7, lo = f == 0 ? o7 : f == 1 ? o8 : o9, hi = f == 0 ? o8 : f == 1 ? o9 : nl;
+        const int f = (int)a - nsrv, lo = f == 0 ? o7 : f == 1 ? o8 : o9, hi = f == 0 ? o8 : f == 1 ? o9 : nl;
         u32 cnt = 0;
         for (int c = 0; c < NC; ++c) cnt += (u32)__builtin_popcountll(range_word<NC>(en, c, lo, hi));
         if (!cnt) continue;

@@ -620,7 +620,6 @@ __global__ __launch_bounds__(64) void k_wsimulate(const WModel M, const WState* 
                                                  u64 seed, int mode, SimCounters* out, i64 rec_beh, WState* rec) {
     u64 steps = 0, trunc = 0, dead = 0;
     const int nl = M.L.off[10];
-    const int o7 = M.L.off[7], o8 = M.L.off[8], o9 = M.L.off[9];
     for (u64 b = (u64)blockIdx.x * 64ull + threadIdx.x; b < n_beh; b += (u64)gridDim.x * 64ull) {
         if (rec_beh >= 0 && (i64)b != rec_beh) continue;
         u64 rs = mix64(seed ^ (b * 0xD1B54A32D192ED03ull));
@@ -638,7 +637,7 @@ __global__ __launch_bounds__(64) void k_wsimulate(const WModel M, const WState* 
             u64 en[WLMASK] = {};
             for (int lane = 0; lane < nl; ++lane)
                 if (wlane(M, buf[cur], lane, nullptr) != W_OFF) en[lane >> 6] |= 1ull << (lane & 63);
-            const int pick = mode == 2 ? tlc_draw<WLMASK>(en, nl, o7, o8, o9, rs)  // TLC's draw
+            const int pick = mode == 2 ? tlc_draw<WLMASK>(en, M.L, M.V, rs)  // TLC's draw
                                        : uniform_draw<WLMASK>(en, excl, rs);
             if (pick < 0) {
                 u64 any = 0;
@@ -688,7 +687,6 @@ __global__ __launch_bounds__(64 * WSIM_WAVES) __attribute__((amdgpu_waves_per_eu
     const int wv = (int)(threadIdx.x >> 6), ln = (int)(threadIdx.x & 63);
     u64 steps = 0, trunc = 0, dead = 0;  // lane 0's tallies
     const int nl = M.L.off[10];
-    const int o7 = M.L.off[7], o8 = M.L.off[8], o9 = M.L.off[9];
     constexpr int NC = (WLANES_MAX + 63) / 64;  // 64-lane chunks of the lane table
     auto copy = [&](WState& d, const WState& s) {  // the whole wave, 8 bytes a lane at a time
         u64* x = reinterpret_cast<u64*>(&d);
@@ -720,7 +718,7 @@ __global__ __launch_bounds__(64 * WSIM_WAVES) __attribute__((amdgpu_waves_per_eu
                 en[c] = __ballot(on);
             }
             static_assert(NC == WLMASK, "one mask word per 64 lanes");
-            const int pick = mode == 2 ? tlc_draw<NC>(en, nl, o7, o8, o9, rs)  // k_wsimulate's draws exactly
+            const int pick = mode == 2 ? tlc_draw<NC>(en, M.L, M.V, rs)  // k_wsimulate's draws exactly
                                        : uniform_draw<NC>(en, excl, rs);
             if (pick < 0) {
                 u64 any = 0;

@@ -4,7 +4,9 @@ Pinned by: the SmokeInit initial-state counts k^9 (Smokeraft.tla:18: 1, 512,
 19683 for k = 1..3), the Smoke domains of every initial state
 (Smokeraft.tla:11-15, 24-76), and every step of replayed behaviours being a
 successor under the Python restatement of Next.  Which successor TLC's
-simulator picks is random, so parity with TLC is distributional only."""
+simulator picks is random, so parity with TLC stays distributional; parity
+with the stated draw rules (include/rmc.h RMC_SIM_*) is exact and is checked in
+test_sim_draws.py against the prediction of tests/sim_rules.py."""
 import ctypes as C
 import hashlib
 import json

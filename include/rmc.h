@@ -24,14 +24,16 @@
 extern "C" {
 #endif
 
-#define RMC_ABI_VERSION 15 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
+#define RMC_ABI_VERSION 16 /* 6: rmc_result.spill_links_on_device (round 5); 7: .verified_spilled, 8: rmc_config.set_bytes and
                               rmc_result.set_slots (round 6); 9: RMC_FLAG_COVERAGE, rmc_coverage, rmc_get_coverage,
                               rmc_coverage_action (round 8); 10: rmc_check_states; 11: rmc_state_keys; 12: RMC_FLAG_CONTINUE,
                               rmc_violations, rmc_get_violations, rmc_trace_violation; 13: RMC_FLAG_SYMMETRY on the wide
                               layout (depth-bounded runs), rmc_state_keys on a wide ctx under it; 14: the state
                               graph: rmc_get_levels, rmc_read_states, rmc_find_states, rmc_graph_edges; 15: model-defined
                               invariants: RMC_FRONT_PREDICATES, rmc_predicates_from_files, rmc_set_predicates,
-                              rmc_eval_predicates, rmc_predicate_error, RMC_INV_USER0 */
+                              rmc_eval_predicates, rmc_predicate_error, RMC_INV_USER0; 16: model-defined
+                              constraints: RMC_FRONT_CONSTRAINTS, rmc_constraints_from_files, rmc_set_constraints,
+                              rmc_constraint_error */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -649,7 +651,8 @@ int rmc_probe_bench(int device, uint64_t table_bytes, uint64_t accesses, int mod
  *    definition references); every conjunct must be one of
  *    `\A i \in Server : currentTerm[i] <= N /\ Len(log[i]) <= N`,
  *    `Cardinality(DOMAIN messages) <= N`, `\A m \in DOMAIN messages :
- *    messages[m] <= N` (<, =<, \leq too); anything else is refused;
+ *    messages[m] <= N` (<, =<, \leq too); anything else is refused (or, under
+ *    RMC_FRONT_CONSTRAINTS, a residual: "model-defined constraints" below);
  *  - INVARIANT(S): TypeOK, or a name from RMC_INV_* whose definition (with the
  *    model definitions it uses) is the compiled-in restatement;
  *  - `BecomeLeader <- Def`: Def must be the compiled-in bug variant;
@@ -732,6 +735,52 @@ const char* rmc_predicates_name(const rmc_predicates* p, int index);
 int rmc_set_predicates(rmc_ctx* ctx, const rmc_predicates* p);
 int rmc_eval_predicates(rmc_ctx* ctx, const rmc_state_view* states, size_t n, uint8_t* verdicts);
 int rmc_predicate_error(const rmc_ctx* ctx);  /* 1 if the reported violation is an evaluation error */
+
+/* ---- model-defined constraints -----------------------------------------------------
+ * RMC_FRONT_CONSTRAINTS: a top-level conjunct of a CONSTRAINT that is none of the four
+ * bounds is not refused but recorded as a *residual* (a note line names each one): the
+ * caller promises to compile the residuals with rmc_constraints_from_files and hand them
+ * to the ctx with rmc_set_constraints.  The recognised bounds stay bounds (they size the
+ * packed layout and run inside the expansion kernel), and a model must still bound all
+ * four fields.  Without the option every refusal stays as it is.
+ *
+ * A residual is a state predicate in the language of the model-defined invariants above,
+ * compiled to the same program format with the same limits and the same refusals with
+ * line and column.  The residuals of all CONSTRAINT names, in order, are one program;
+ * residual r carries the name of the CONSTRAINT of the .cfg it came from.
+ *
+ * Semantics (TLC's): a successor that fails a residual counts in rmc_result.generated
+ * and nowhere else: it is not stored, not counted in distinct, not expanded, not left on
+ * the queue and never reported by an invariant, built-in or model-defined; its
+ * fingerprint stays in the set, so later copies are dropped as duplicates.  A level
+ * whose states are all filtered adds nothing to depth.  An initial state that fails
+ * gives distinct 0, generated 1, depth 0.  The filter is a pass of its own after the
+ * seed and after every expansion launch (the expansion kernels are unchanged; they run
+ * with the fused invariant check off and without commuting-diamond skipping, and the
+ * built-in invariants are checked by a pass over the kept states); without constraints
+ * nothing is allocated, launched or read back for them.
+ * An evaluation error in a residual (verdict 2) keeps the state and stops the search at
+ * the end of its level: rmc_run_bfs returns 0, rmc_constraint_error is 1 + the
+ * residual's index (0: none) and rmc_trace leads to the state.
+ *
+ * rmc_constraints_from_files: rmc_model_from_files' arguments; the residuals as an
+ * rmc_predicates (rmc_predicates_count / _name / _free apply); count 0: the model has
+ * none.  rmc_set_constraints copies the program into the ctx (NULL or count 0 removes
+ * it).  Single GPU, packed layout, resident store.  RMC_E_INVAL, each named with its
+ * reason: RMC_FLAG_VERIFY_STATES (a removed state's set slot never gets an owner),
+ * RMC_FLAG_CONTINUE, RMC_FLAG_COVERAGE, RMC_FLAG_SPILL, a wide ctx, a sharded ctx (and
+ * rmc_shard after constraints are set), under RMC_FLAG_SYMMETRY a residual that names a
+ * server model value, a program compiled for another n_servers; RMC_E_STATE on a ctx
+ * with a checkpoint loaded (rmc_recover rebuilt its set from the stored states).  With
+ * constraints set rmc_simulate, rmc_checkpoint and rmc_recover are RMC_E_STATE, and after
+ * a run with constraints rmc_graph_edges and rmc_find_states are (that run's set holds
+ * keys without a stored state, whether or not the constraints are still set);
+ * rmc_get_levels and rmc_read_states show the kept states only. */
+#define RMC_FRONT_CONSTRAINTS (1u << 4)
+int rmc_constraints_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                               uint32_t options, rmc_predicates** out, char* err, size_t err_cap);
+int rmc_set_constraints(rmc_ctx* ctx, const rmc_predicates* p);
+int rmc_constraint_error(const rmc_ctx* ctx);  /* 1 + the residual whose evaluation failed, 0: none */
 
 /* rmc_model_from_files for BFS / simulation models with raft_path = NULL and
  * RMC_FRONT_BUILTIN_RAFT taken from the environment (RMC_BUILTIN_RAFT=1).

@@ -140,7 +140,7 @@ int seed_init(rmc_ctx* c) {
     std::string why;
     if (encode_view(c->sh.S, c->sh.K, iv, packed.data(), &why)) return fail(c, RMC_E_INVAL, why);
     HIPCHK(c, hipMemcpyAsync(c->d_staged, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, c->k->seed(c->sh.sym, c->P, c->PT, c->B, c->d_staged, 1, c->st));
+    HIPCHK(c, c->k->seed(c->sh.sym, expand_params(c), c->PT, c->B, c->d_staged, 1, c->st));
     return 0;
 }
 
@@ -259,6 +259,8 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
     scan_target(c, &k, 1, *depth);
     if (pred_on(c))
         if (int rc = pred_scan(c, *depth)) return rc;
+    if (cons_on(c))  // (the level's kept states: [hi, count))
+        if (int rc = cons_scan(c, *depth, hi)) return rc;
     if (cb) {
         rmc_level_stats ls{};
         ls.level = nnew ? *depth - 1 : *depth;
@@ -454,6 +456,7 @@ void rmc_destroy(rmc_ctx* c) {
     (void)hipFree(c->d_cov);
     (void)hipFree(c->d_viol);
     pred_free(c);
+    cons_free(c);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -483,6 +486,8 @@ static int start_run(rmc_ctx* c, int* depth) {
         if (int rc = viol_begin(c)) return rc;
     if (pred_on(c))
         if (int rc = pred_begin(c)) return rc;
+    if (cons_on(c))
+        if (int rc = cons_begin(c)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
@@ -490,6 +495,10 @@ static int start_run(rmc_ctx* c, int* depth) {
     // ---- Init (raft.tla:125-129): one initial state
     if (int rc = seed_init(c)) return rc;
     if (int rc = read_counters(c)) return rc;
+    if (cons_on(c)) {  // an initial state that fails the constraint is generated and dropped: depth 0
+        if (int rc = cons_pass(c, 0, c->h_ctr->count)) return rc;
+        if (int rc = read_counters(c)) return rc;  // (the built-in invariants of the kept states)
+    }
     *depth = seed_done(c);
     if (c->sh.verify) HIPCHK(c, c->k->publish(c->sh.sym, c->P, c->PT, c->B, 0, c->h_ctr->count, c->st));
     if (cover_on(c))  // row Init: the one initial state generated, and what the seed stored
@@ -500,6 +509,8 @@ static int start_run(rmc_ctx* c, int* depth) {
         if (int rc = pred_pass(c, 0, c->h_ctr->count)) return rc;
         if (int rc = pred_scan(c, 1)) return rc;
     }
+    if (cons_on(c))
+        if (int rc = cons_scan(c, 1, 0)) return rc;
     return 0;
 }
 
@@ -508,6 +519,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     // the state graph calls (rmc_graph.cpp) read a completed run only: its index is built on demand
     c->run_done = 0;
+    c->run_cons = cons_on(c) ? 1 : 0;
     c->graph_idx = 0;
     c->run_seed = c->cfg.seed;
     if (c->wide || c->dist.on) {
@@ -525,6 +537,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool cover = cover_on(c);  // (rmc_recover refuses the flags: never a resumed run)
     const bool cont = continue_on(c);
     const bool preds = pred_on(c);  // (rmc_recover refuses a ctx with predicates too)
+    const bool cons = cons_on(c);   // (and one with constraints)
     int depth = 0;
     if (resume) {
         c->res.left_on_queue = 0;
@@ -547,7 +560,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     }();
     const LevelText text = {"verification: a stored state has no fingerprint slot", "symmetry tie buffer full", "states",
                             &c->walked};
-    for (int more = 1; more && !c->stop;) {
+    for (int more = depth > 0; more && !c->stop;) {  // (depth 0: the constraint dropped the initial state)
         const u64 lo = c->level_start[depth - 1], hi = c->level_start[depth];
         if (lo == hi) break;  // fixpoint
         if (c->cfg.max_depth > 0 && depth >= c->cfg.max_depth) {
@@ -626,13 +639,13 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                 // coverage reads Counters.count back after every launch, so it is current here
                 const u64 cov_before = c->h_ctr->count;
                 if (resumed) {
-                    HIPCHK(c, c->k->expand_resume(c->P, c->PT, c->B, a, b, c->st));
+                    HIPCHK(c, c->k->expand_resume(expand_params(c), c->PT, c->B, a, b, c->st));
                 } else {
-                    HIPCHK(c, c->k->expand(c->sh.sym, c->sh.verify, c->P, c->PT, c->B, a, b, c->st));
+                    HIPCHK(c, c->k->expand(c->sh.sym, c->sh.verify, expand_params(c), c->PT, c->B, a, b, c->st));
                 }
                 c->res.expand_launches += 1;
                 if (c->sh.sym && !c->sh.verify) {
-                    HIPCHK(c, c->k->ties(c->P, c->PT, c->B, c->st));
+                    HIPCHK(c, c->k->ties(expand_params(c), c->PT, c->B, c->st));
                     HIPCHK(c, hipMemsetAsync(&c->B.ctr->nties, 0, 8, c->st));
                 }
                 if (c->sh.verify) {
@@ -659,7 +672,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                         c->res.spills = cnt / win;  // passes of the ring
                     }
                 }
-                if (cover || cont || preds) {
+                if (cover || cont || preds || cons) {
                     // the coverage pass of this launch: its parents [a, b) are still resident
                     // (the store; the linear window, which moves only [base, a) and before the
                     // launch; the ring, whose room is relative to a: a launch stopped on
@@ -671,6 +684,10 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                         if (int rc = read_counters(c)) return rc;
                         if (c->h_ctr->overflow || c->h_ctr->table_full) { abort_level = true; break; }
                     }
+                    // the constraint pass first: whatever follows reads the kept states only (it
+                    // reads the counters back: count = the kept states' end)
+                    if (cons)
+                        if (int rc = cons_pass(c, cov_before, c->h_ctr->count)) return rc;
                     if (cover)
                         HIPCHK(c, c->k->cover(c->P, c->B, resumed ? b : a, b, cov_before, c->h_ctr->count, 0, c->d_cov,
                                               c->st));
@@ -705,6 +722,8 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
         if (int rc = cover_end(c)) return rc;
     if (cont)
         if (int rc = viol_end(c)) return rc;
+    if (cons)
+        if (int rc = cons_end(c)) return rc;
     const double D = (double)c->res.distinct, G = (double)c->res.generated;
     // TLC's "calculated (optimistic)" fingerprint-collision estimate
     c->res.collision_probability = fp_collision_estimate(D, G, c->table_slots, c->set_epoch != 0);
@@ -860,6 +879,9 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
     if (pred_on(c))
         return fail(c, RMC_E_STATE, "simulation does not evaluate model-defined invariants (rmc_set_predicates(ctx, NULL) "
                                     "removes them)");
+    if (cons_on(c))
+        return fail(c, RMC_E_STATE, "simulation does not evaluate model-defined constraints (rmc_set_constraints(ctx, "
+                                    "NULL) removes them)");
     if (c->wide) return sim_wide(c, sc, out, rec_beh, wrec);
     if (sc->mode == RMC_SIM_TLC)
         return fail(c, RMC_E_INVAL, "RMC_SIM_TLC draws on the wide layout only (bounds beyond the packed capacity)");

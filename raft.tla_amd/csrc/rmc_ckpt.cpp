@@ -77,6 +77,8 @@ int rmc_checkpoint(rmc_ctx* c, const char* path) {
     if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
     if (pred_on(c))
         return fail(c, RMC_E_STATE, "checkpoint: not supported with model-defined invariants set (rmc_set_predicates)");
+    if (cons_on(c))
+        return fail(c, RMC_E_STATE, "checkpoint: not supported with model-defined constraints set (rmc_set_constraints)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_COVERAGE (the tallies are of whole "
                                     "runs and are not written)");
@@ -137,6 +139,9 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     if (c->wide) return fail(c, RMC_E_STATE, "checkpoint / recover: not supported on the wide layout");
     if (pred_on(c))
         return fail(c, RMC_E_STATE, "recover: not supported with model-defined invariants set (rmc_set_predicates)");
+    if (cons_on(c))
+        return fail(c, RMC_E_STATE, "recover: not supported with model-defined constraints set (rmc_set_constraints): "
+                                    "recovery rebuilds the set from the stored states, without the removed ones' keys");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_COVERAGE (the tallies are of whole runs)");
     if (c->cfg.flags & RMC_FLAG_CONTINUE)

@@ -163,11 +163,26 @@ struct rmc_ctx {
     rmc::pred::Program* d_prog = nullptr;
     unsigned long long* d_pword = nullptr;
     int pred_error = 0;
+    // model-defined constraints (rmc_set_constraints; rmc_cons.cpp, rmc_dev_cons.h): the ctx's copy of
+    // the residuals' program and names, the program in device memory, the pass's word (min over the
+    // states a residual's evaluation failed on), its scratch for launches of up to cons_cap new states
+    // — all allocated by rmc_set_constraints and the passes only — the Params its expansion launches
+    // run with (no fused invariant check, no commuting-diamond skipping), and 1 + the residual whose
+    // evaluation stopped the last run
+    rmc_predicates* cons = nullptr;
+    rmc::pred::Program* d_cprog = nullptr;
+    unsigned long long* d_cword = nullptr;
+    rmc::ConsBufs CB{};
+    rmc::u64 cons_cap = 0;
+    rmc::Params PE{};
+    int cons_error = 0;
+    rmc::u64 cons_passes = 0, cons_removed = 0;  // the last run's passes and the states they removed
     // state graph export (rmc_graph.cpp): a completed rmc_run_bfs whose store, links and set the
     // calls may read; its fingerprint salt (rmc_set_seed may change cfg.seed after it); and whether
     // B.sidx maps every stored state's set slot to its index — a verification run leaves it so, any
     // other ctx builds it at its first graph call (one k_publish pass); every rmc_run_bfs resets both
     int run_done = 0;
+    int run_cons = 0;  // ... and it ran with constraints: its set holds keys of removed states, which no stored state owns
     int graph_idx = 0;
     rmc::u64 run_seed = 0;
     rmc_result res{};
@@ -238,6 +253,20 @@ int pred_begin(rmc_ctx* c);
 int pred_pass(rmc_ctx* c, rmc::u64 nlo, rmc::u64 nhi);
 int pred_scan(rmc_ctx* c, int depth);
 void pred_free(rmc_ctx* c);
+// Model-defined constraints (packed layout, resident store): at the start of a run the word
+// cleared and PE set; the pass over the states a launch (or the seed) added, [nlo, nhi) — filter,
+// in-place compaction, Counters read back (count = nlo + kept), then the built-in invariants over
+// the kept states (launched, not waited for); at a level's end (after scan_target and
+// pred_scan) the word read back: an evaluation error stops the search, the target the least kept
+// state of the level [level_lo, count) on which a residual's evaluation fails.
+inline bool cons_on(const rmc_ctx* c) { return c->cons != nullptr; }
+// The Params of the seed and expansion launches.
+inline const rmc::Params& expand_params(const rmc_ctx* c) { return c->cons ? c->PE : c->P; }
+int cons_begin(rmc_ctx* c);
+int cons_pass(rmc_ctx* c, rmc::u64 nlo, rmc::u64 nhi);
+int cons_scan(rmc_ctx* c, int depth, rmc::u64 level_lo);
+int cons_end(rmc_ctx* c);  // RMC_CONS_STATS: one stderr line of the run's passes, states removed and moved
+void cons_free(rmc_ctx* c);
 int pred_eval_wide(rmc_ctx* c, const rmc_state_view* states, size_t n, uint8_t* d_out);  // rmc_wide.cpp
 // After the seed launch's read_counters, on either layout: level 1 is the states
 // it stored, and an invariant Init violates is the target.  Returns the depth.

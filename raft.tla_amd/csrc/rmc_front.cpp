@@ -591,10 +591,12 @@ void set_min(int* dst, int v) { *dst = (*dst < 0 || v < *dst) ? v : *dst; }
 // options: RMC_FRONT_BUILTIN_RAFT (1) accept a model whose raft.tla is not on
 // disk, using the compiled-in one; RMC_FRONT_SIMULATE (2) simulation model;
 // RMC_FRONT_PREDICATES (8) accept INVARIANTs of the model's own.  preds != nullptr:
-// compile those into it (rmc_predicates_from_files).
+// compile those into it (rmc_predicates_from_files).  RMC_FRONT_CONSTRAINTS (16) record the
+// CONSTRAINT conjuncts that are no bound as residuals.  cons != nullptr: compile those
+// into it (rmc_constraints_from_files).
 static int parse_model(const char* cfg_path, const char* tla_path, const char* raft_path, uint32_t options,
                        rmc_config* out, rmc_sim_config* sim, char* info, size_t info_cap,
-                       rmc_predicates* preds = nullptr) {
+                       rmc_predicates* preds = nullptr, rmc_predicates* cons = nullptr) {
     std::string e;
     auto fail = [&](const std::string& m) {
         if (info && info_cap) snprintf(info, info_cap, "%s", m.c_str());
@@ -779,6 +781,11 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
     // ---- CONSTRAINT -> bounds
     Bounds bd;
     const std::string server_set = server_via;  // `\A i \in <Server or its set definition>`
+    // RMC_FRONT_CONSTRAINTS: the conjuncts that are no bound, in order, each under the cfg's
+    // CONSTRAINT name it came from (a part of a `\A i \in Server :` conjunct keeps the quantifier)
+    const bool keep_residuals = (options & RMC_FRONT_CONSTRAINTS) != 0;
+    std::vector<Residual> residuals;
+    std::string cfg_constraint;
     std::function<int(const std::string&, const Unit&, const std::vector<Tok>&, size_t, size_t, int)> item;
     auto atom_bound = [&](const std::vector<Tok>& v, size_t a, size_t b, const std::string& var, int* dst_kind,
                           int* val) -> bool {
@@ -809,6 +816,20 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         };
         if (a >= b) return refuse("is empty");
         if (depth > 16) return refuse("nests too deeply");
+        // no bound: refused, or the residual `head part` (head: a quantifier prefix [h0, h1) or nothing)
+        auto other = [&](const std::string& why, size_t p, size_t q, size_t h0 = 0, size_t h1 = 0) {
+            if (!keep_residuals) return refuse(why);
+            Residual r;
+            r.name = cfg_constraint;
+            r.toks.assign(v.begin() + (long)h0, v.begin() + (long)h1);
+            r.toks.insert(r.toks.end(), v.begin() + (long)p, v.begin() + (long)q);
+            r.text = join(r.toks, 0, r.toks.size());
+            r.line = v[p].line;
+            notes.push_back("CONSTRAINT " + cfg_constraint + ": residual " + std::to_string(residuals.size()) + " `" +
+                            r.text + "` (line " + std::to_string(r.line) + ") is filtered by the constraint pass");
+            residuals.push_back(r);
+            return 0;
+        };
         if (v[a].t == "(") {  // a parenthesised conjunct: its own conjuncts
             int dd = 0;
             size_t k = a;
@@ -825,7 +846,7 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         // a definition reference: splice its conjuncts
         if (b - a == 1 && (isalpha((unsigned char)v[a].t[0]) || v[a].t[0] == '_')) {
             const Unit* d = X.def(v[a].t);
-            if (!d) return refuse("names no definition of the model");
+            if (!d) return other("names no definition of the model", a, b);
             const std::set<std::string> ids = idents(d->body());
             bool touches_state = false;
             for (const char* sv2 : kStateVars) touches_state |= ids.count(sv2) > 0;
@@ -846,9 +867,13 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
             const std::string var = v[a + 1].t;
             for (const auto& [p, q] : split_conj(v, a + 5, b)) {
                 int kind = -1, val = 0;
-                if (!atom_bound(v, p, q, var, &kind, &val))
-                    return refuse("has a part `" + join(v, p, q) +
-                                  "` that is not currentTerm[" + var + "] <= N or Len(log[" + var + "]) <= N");
+                if (!atom_bound(v, p, q, var, &kind, &val)) {
+                    if (int rc = other("has a part `" + join(v, p, q) + "` that is not currentTerm[" + var +
+                                           "] <= N or Len(log[" + var + "]) <= N",
+                                       p, q, a, a + 5))
+                        return rc;
+                    continue;
+                }
                 set_min(kind == 0 ? &bd.term : &bd.log, val);
             }
             return 0;
@@ -859,10 +884,10 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
             v[a + 8].t == v[a + 1].t && v[a + 9].t == "]") {
             int n;
             const std::string& op = v[a + 10].t;
-            if (!X.int_of(v[a + 11].t, &n)) return refuse("bound " + v[a + 11].t + " is not a number");
+            if (!X.int_of(v[a + 11].t, &n)) return other("bound " + v[a + 11].t + " is not a number", a, b);
             if (op == "<=" || op == "=<" || op == "\\leq") set_min(&bd.dup, n);
             else if (op == "<") set_min(&bd.dup, n - 1);
-            else return refuse("is not messages[m] <= N");
+            else return other("is not messages[m] <= N", a, b);
             return 0;
         }
         // Cardinality(DOMAIN messages) <= N   (or BagToSet(messages))
@@ -872,22 +897,23 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
             else if (b - a >= 9 && v[k].t == "BagToSet" && v[k + 1].t == "(" && v[k + 2].t == "messages" &&
                      v[k + 3].t == ")" && v[k + 4].t == ")")
                 k += 5;
-            else return refuse("is not Cardinality(DOMAIN messages) <= N");
-            if (k + 2 != b) return refuse("is not Cardinality(DOMAIN messages) <= N");
+            else return other("is not Cardinality(DOMAIN messages) <= N", a, b);
+            if (k + 2 != b) return other("is not Cardinality(DOMAIN messages) <= N", a, b);
             int n;
-            if (!X.int_of(v[k + 1].t, &n)) return refuse("bound " + v[k + 1].t + " is not a number");
+            if (!X.int_of(v[k + 1].t, &n)) return other("bound " + v[k + 1].t + " is not a number", a, b);
             if (v[k].t == "<=" || v[k].t == "=<" || v[k].t == "\\leq") set_min(&bd.msgs, n);
             else if (v[k].t == "<") set_min(&bd.msgs, n - 1);
-            else return refuse("is not Cardinality(DOMAIN messages) <= N");
+            else return other("is not Cardinality(DOMAIN messages) <= N", a, b);
             return 0;
         }
-        return refuse("is not a state bound the engine implements (currentTerm[i] <= N, Len(log[i]) <= N, "
-                      "Cardinality(DOMAIN messages) <= N, messages[m] <= N, conjoined)");
+        return other("is not a state bound the engine implements (currentTerm[i] <= N, Len(log[i]) <= N, "
+                      "Cardinality(DOMAIN messages) <= N, messages[m] <= N, conjoined)", a, b);
     };
     for (const auto& cn : C.constraints) {
         const Unit* d = X.def(cn);
         if (!d) return fail("CONSTRAINT " + cn + ": definition not found");
         std::vector<Tok> one{{cn, d->line, 1}};
+        cfg_constraint = cn;
         if (int rc = item(cn, *d, one, 0, 1, 0)) return fail(e), rc;
     }
     g.max_term = bd.term;
@@ -965,6 +991,10 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         std::string why;
         if (!compile_predicates(X, user_invs, server_elems, elems, preds, &why)) return fail(why);
     }
+    if (cons) {
+        std::string why;
+        if (!compile_residuals(X, residuals, server_elems, elems, cons, &why)) return fail(why);
+    }
     *out = g;
     if (info && info_cap) {
         std::string all;
@@ -997,6 +1027,24 @@ extern "C" int rmc_predicates_from_files(const char* cfg_path, const char* tla_p
     rmc_sim_config sim;
     if (int rc = parse_model(cfg_path, tla_path, raft_path, options | RMC_FRONT_PREDICATES, &cfg, &sim, err, err_cap,
                              p.get()))
+        return rc;
+    if (err && err_cap) err[0] = 0;
+    *out = p.release();
+    return 0;
+}
+
+extern "C" int rmc_constraints_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                                          uint32_t options, rmc_predicates** out, char* err, size_t err_cap) {
+    if (!out) {
+        if (err && err_cap) snprintf(err, err_cap, "null argument");
+        return RMC_E_PARSE;
+    }
+    *out = nullptr;
+    std::unique_ptr<rmc_predicates> p(new rmc_predicates());
+    rmc_config cfg;
+    rmc_sim_config sim;
+    if (int rc = parse_model(cfg_path, tla_path, raft_path, options | RMC_FRONT_CONSTRAINTS, &cfg, &sim, err, err_cap,
+                             nullptr, p.get()))
         return rc;
     if (err && err_cap) err[0] = 0;
     *out = p.release();

@@ -126,6 +126,9 @@ int rmc_find_states(rmc_ctx* c, const rmc_state_view* states, size_t n, uint64_t
     if (!c) return RMC_E_INVAL;
     if (n && (!states || !index)) return fail(c, RMC_E_INVAL, "rmc_find_states: states or index is NULL");
     if (int rc = graph_ready(c, "rmc_find_states", false)) return rc;
+    if (c->run_cons)
+        return fail(c, RMC_E_STATE, "rmc_find_states: the run had model-defined constraints set (rmc_set_constraints): its set "
+                                    "holds the keys of removed states, which no stored state owns");
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const u64 NW = (u64)c->NW, chunk = std::min<u64>(n, chunk_states(kStateChunk));
@@ -151,6 +154,9 @@ int rmc_graph_edges(rmc_ctx* c, uint64_t lo, uint64_t hi, rmc_edge* out, size_t 
     if (!n_out || (cap && !out)) return fail(c, RMC_E_INVAL, "rmc_graph_edges: n_out or out is NULL");
     *n_out = 0;
     if (int rc = graph_ready(c, "rmc_graph_edges", false)) return rc;
+    if (c->run_cons)
+        return fail(c, RMC_E_STATE, "rmc_graph_edges: the run had model-defined constraints set (rmc_set_constraints): its set "
+                                    "holds the keys of removed states, which no stored state owns");
     if (c->stop)
         return fail(c, RMC_E_STATE,
                     "rmc_graph_edges: the run stopped at a violation or a deadlock, so which states it expanded is "

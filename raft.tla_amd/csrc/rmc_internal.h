@@ -100,6 +100,17 @@ struct DevBufs {
     u32 admit_reserve;
 };
 
+// The constraint pass's scratch of one launch's n new states (rmc_dev_cons.h; allocated by
+// rmc_set_constraints' ctx only, grown to the largest launch): a keep byte per state, the kept
+// count of each tile of 256 and their exclusive scan (off[tiles]: the kept states in all), and
+// the head's holes in rank order (at most n / 2).
+struct ConsBufs {
+    uint8_t* keep;
+    u32* cnt;
+    u64* off;
+    u64* dst;
+};
+
 struct PermTable {
     u32 code[120];  // every server permutation (old id -> new id), 3 bits per id, S <= 5
     int np;         // S!
@@ -178,6 +189,15 @@ struct ShapeKernels {
     hipError_t (*pred)(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* word,
                        hipStream_t st);
     hipError_t (*pred_eval)(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st);
+    // model-defined constraints (rmc_dev_cons.h; prog: the residuals' program in device memory): the
+    // states a launch added, [nlo, nhi), filtered and compacted in place — afterwards [nlo, nlo + kept)
+    // holds the kept states with their links and Counters.count = nlo + kept; word = min (index << 8 |
+    // residual << 1 | 1) over the states a residual's evaluation failed on (their index before the
+    // move), word[1] += the states moved.  cons_inv: the built-in invariants of P.inv_mask on the kept states [lo, hi), into
+    // Counters.viol as the fused check writes it
+    hipError_t (*cons)(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi, const ConsBufs& C,
+                       unsigned long long* word, hipStream_t st);
+    hipError_t (*cons_inv)(const Params& P, const DevBufs& B, u64 lo, u64 hi, hipStream_t st);
     // keys[t] = the key of in[t] (P.fp_mask applied); ref != nullptr: same[t] = in[t] compares equal to
     // the record in[ref[t]] (k_keys, rmc_dev_tools.h)
     hipError_t (*keys)(bool sym, const Params& P, const PermTable& PT, const u32* in, u64 n, u64* keys,

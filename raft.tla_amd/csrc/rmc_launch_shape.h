@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "rmc_dev_cons.h"
 #include "rmc_dev_expand.h"
 #include "rmc_dev_graph.h"
 #include "rmc_dev_pred.h"
@@ -54,6 +55,30 @@ static hipError_t launch_pred_t(const pred::Program* prog, const DevBufs& B, u64
     const u64 blocks = (nhi - nlo + kPredThreads - 1) / kPredThreads;
     hipLaunchKernelGGL((k_pred<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kPredThreads), 0, st, prog,
                        B, nlo, nhi, word);
+    return hipGetLastError();
+}
+
+// The constraint pass of one expansion launch (or of the seed step) over the states it added:
+// the filter, the scan of its tile counts, the holes, the move.
+template <int S, int K>
+static hipError_t launch_cons_t(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi, const ConsBufs& C,
+                                unsigned long long* word, hipStream_t st) {
+    if (nhi <= nlo) return hipSuccess;
+    const u64 n = nhi - nlo, nt = cons::tiles(n);
+    const unsigned grid = (unsigned)(nt < 2048 ? nt : 2048);
+    hipLaunchKernelGGL((k_cons<S, K>), dim3(grid), dim3(kPredThreads), 0, st, prog, B, nlo, nhi, C, word);
+    if (hipError_t e = launch_graph_scan(C.cnt, nt, C.off, st)) return e;
+    hipLaunchKernelGGL((k_cons_holes<S, K>), dim3(grid), dim3(256), 0, st, n, C);
+    hipLaunchKernelGGL((k_cons_move<S, K>), dim3(grid), dim3(256), 0, st, B, nlo, n, C, word + 1);
+    return hipGetLastError();
+}
+
+template <int S, int K>
+static hipError_t launch_cons_inv_t(const Params& P, const DevBufs& B, u64 lo, u64 hi, hipStream_t st) {
+    if (hi <= lo) return hipSuccess;
+    const u64 blocks = (hi - lo + 255) / 256;
+    hipLaunchKernelGGL((k_cons_inv<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, P, B, lo,
+                       hi);
     return hipGetLastError();
 }
 
@@ -295,6 +320,8 @@ static ShapeKernels shape_table() {
     k.check = launch_check_t<S, K>;
     k.pred = launch_pred_t<S, K>;
     k.pred_eval = launch_pred_eval_t<S, K>;
+    k.cons = launch_cons_t<S, K>;
+    k.cons_inv = launch_cons_inv_t<S, K>;
     k.keys = launch_keys_t<S, K>;
     k.set_salt = set_object_salt;
     k.graph_count = [](const Params& P, const DevBufs& B, u64 lo, u64 hi, u32* cnt, hipStream_t st) {

@@ -376,6 +376,14 @@ public:
         if (t != T_BOOL) throw PredError{"the predicate is not Boolean (it is a " + std::string(ty_name(t)) + ")"};
         emit(rmc::pred::OP_HALT, 0, 0);
     }
+    // a CONSTRAINT's residual conjunct: its tokens as they stand in the model (no parameters in scope)
+    void residual(const std::vector<Tok>& toks) {
+        PEnv top;
+        depth = 0;
+        const PTy t = gen(PredParser(toks).parse_all(), top);
+        if (t != T_BOOL) throw PredError{"the conjunct is not Boolean (it is a " + std::string(ty_name(t)) + ")"};
+        emit(rmc::pred::OP_HALT, 0, 0);
+    }
 
 private:
     [[noreturn]] static void refuse(const std::string& what, const PNodeP& n) {
@@ -877,49 +885,82 @@ private:
     }
 };
 
-// Compiles the INVARIANTs `names` (definitions of the model) into *out; on failure the
-// message names the invariant, the construct, and its line and column.
-inline bool compile_predicates(const Ctx& X, const std::vector<std::string>& names,
-                               const std::vector<std::string>& servers, const std::vector<std::string>& values,
-                               rmc_predicates* out, std::string* err) {
+// One predicate of a program: an INVARIANT (a definition of the model, toks == nullptr) or a
+// CONSTRAINT's residual conjunct (its tokens).
+struct PredItem {
+    std::string name, label;  // the program's name of it; how messages call it
+    const std::vector<Tok>* toks;
+};
+
+// A conjunct of a CONSTRAINT that is no bound (rmc_front.cpp, RMC_FRONT_CONSTRAINTS).
+struct Residual {
+    std::string name;  // the cfg's CONSTRAINT it came from
+    std::vector<Tok> toks;
+    std::string text;
+    int line = 0;
+};
+
+// Compiles `items` into *out; on failure the message names the item, the construct, and its
+// line and column.  what: "model-defined invariants" / "residual constraint conjuncts".
+inline bool compile_program(const Ctx& X, const std::vector<PredItem>& items, const char* what,
+                            const std::vector<std::string>& servers, const std::vector<std::string>& values,
+                            rmc_predicates* out, std::string* err) {
     using namespace rmc::pred;
     memset(out, 0, sizeof *out);
     out->prog.n_servers = (int)servers.size();
-    if ((int)names.size() > PRED_MAX) {
-        *err = std::to_string(names.size()) + " model-defined invariants exceed RMC_MAX_PREDICATES = " +
-               std::to_string(PRED_MAX);
+    if ((int)items.size() > PRED_MAX) {
+        *err = std::to_string(items.size()) + " " + what + " exceed RMC_MAX_PREDICATES = " + std::to_string(PRED_MAX);
         return false;
     }
     std::vector<uint32_t> code;
     PredGen g(X, servers, values, code);
-    for (size_t p = 0; p < names.size(); ++p) {
+    for (size_t p = 0; p < items.size(); ++p) {
+        const std::string& label = items[p].label;
         out->prog.entry[p] = (int)code.size();
         try {
-            g.predicate(names[p]);
+            if (items[p].toks) g.residual(*items[p].toks);
+            else g.predicate(items[p].name);
         } catch (const PredError& e) {
-            *err = "INVARIANT " + names[p] + ": " + e.msg + " is not in the predicate language (rmc.h \"model-defined invariants\")";
+            *err = label + ": " + e.msg + " is not in the predicate language (rmc.h \"model-defined invariants\")";
             return false;
         }
         if (g.stack_depth() > PRED_STACK) {
-            *err = "INVARIANT " + names[p] + ": evaluation stack depth " + std::to_string(g.stack_depth()) +
-                   " exceeds " + std::to_string(PRED_STACK);
+            *err = label + ": evaluation stack depth " + std::to_string(g.stack_depth()) + " exceeds " +
+                   std::to_string(PRED_STACK);
             return false;
         }
         if (g.bound_names() > PRED_BOUND) {
-            *err = "INVARIANT " + names[p] + ": " + std::to_string(g.bound_names()) + " bound names exceed " +
-                   std::to_string(PRED_BOUND);
+            *err = label + ": " + std::to_string(g.bound_names()) + " bound names exceed " + std::to_string(PRED_BOUND);
             return false;
         }
         if ((int)code.size() > PRED_CODE) {
-            *err = "INVARIANT " + names[p] + ": " + std::to_string(code.size()) + " code words in all exceed " +
-                   std::to_string(PRED_CODE);
+            *err = label + ": " + std::to_string(code.size()) + " code words in all exceed " + std::to_string(PRED_CODE);
             return false;
         }
-        snprintf(out->name[p], sizeof out->name[p], "%s", names[p].c_str());
+        snprintf(out->name[p], sizeof out->name[p], "%s", items[p].name.c_str());
     }
-    out->prog.n_pred = (int)names.size();
+    out->prog.n_pred = (int)items.size();
     out->prog.n_code = (int)code.size();
     for (size_t q = 0; q < code.size(); ++q) out->prog.code[q] = code[q];
     out->names_server = g.names_server;
     return true;
+}
+
+// The INVARIANTs `names` (definitions of the model).
+inline bool compile_predicates(const Ctx& X, const std::vector<std::string>& names,
+                               const std::vector<std::string>& servers, const std::vector<std::string>& values,
+                               rmc_predicates* out, std::string* err) {
+    std::vector<PredItem> items;
+    for (const auto& n : names) items.push_back({n, "INVARIANT " + n, nullptr});
+    return compile_program(X, items, "model-defined invariants", servers, values, out, err);
+}
+
+// The residual conjuncts of the model's CONSTRAINTs, in order.
+inline bool compile_residuals(const Ctx& X, const std::vector<Residual>& residuals,
+                              const std::vector<std::string>& servers, const std::vector<std::string>& values,
+                              rmc_predicates* out, std::string* err) {
+    std::vector<PredItem> items;
+    for (const auto& r : residuals)
+        items.push_back({r.name, "CONSTRAINT " + r.name + ": conjunct `" + r.text + "`", &r.toks});
+    return compile_program(X, items, "residual constraint conjuncts", servers, values, out, err);
 }

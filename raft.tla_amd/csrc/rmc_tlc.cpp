@@ -437,6 +437,9 @@ int main(int argc, char** argv) {
     // INVARIANTs of the model's own (none of the ten compiled-in ones) are compiled to the
     // predicate interpreter's bytecode and checked by a pass of the single-GPU search
     fopts |= RMC_FRONT_PREDICATES;
+    // CONSTRAINT conjuncts that are none of the four bounds (residuals) are compiled the same way
+    // and filter what the single-GPU search stores, in a pass after each of its launches
+    fopts |= RMC_FRONT_CONSTRAINTS;
     if (depth > 0 && !simulate) fopts |= RMC_FRONT_DEPTH_BOUNDED;
     rmc_predicates* preds = nullptr;
     {
@@ -447,6 +450,27 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
+    // (a model with residuals is refused by its constraint first)
+    rmc_predicates* cons = nullptr;
+    {
+        char cerr[2048];
+        if (rmc_constraints_from_files(cfg.c_str(), tla.c_str(), raft.empty() ? nullptr : raft.c_str(),
+                                       fopts | (simulate ? RMC_FRONT_SIMULATE : 0u), &cons, cerr, sizeof cerr)) {
+            printf("Error: %s\n", cerr);
+            rmc_predicates_free(preds);
+            return 1;
+        }
+    }
+    const int ncons = rmc_predicates_count(cons);
+    if (ncons && (verify || cont || coverage || !dump.empty() || gpus > 1 || simulate || !ckpt.empty() || !recover.empty())) {
+        printf("Error: CONSTRAINT %s has a conjunct that is no bound and is filtered by the single-GPU search's "
+               "constraint pass: not with %s\n", rmc_predicates_name(cons, 0),
+               verify ? "-verify" : cont ? "-continue" : coverage ? "-coverage" : !dump.empty() ? "-dump"
+               : gpus > 1 ? "-gpus N > 1" : simulate ? "-simulate" : !ckpt.empty() ? "-checkpoint" : "-recover");
+        rmc_predicates_free(preds);
+        rmc_predicates_free(cons);
+        return 1;
+    }
     const int npred = rmc_predicates_count(preds);
     if (npred && (cont || gpus > 1 || simulate || !ckpt.empty() || !recover.empty())) {
         printf("Error: INVARIANT %s is defined by the model and checked by the single-GPU search's predicate pass: "
@@ -454,6 +478,7 @@ int main(int argc, char** argv) {
                cont ? "-continue" : gpus > 1 ? "-gpus N > 1" : simulate ? "-simulate" : !ckpt.empty() ? "-checkpoint"
                                                                                                      : "-recover");
         rmc_predicates_free(preds);
+        rmc_predicates_free(cons);
         return 1;
     }
     if (simulate) return run_simulation(cfg, tla, raft, fopts, device, depth, num, seed);
@@ -492,8 +517,11 @@ int main(int argc, char** argv) {
     if (!dump.empty() && !capacity && !fpmem) c.state_capacity = 1ull << 26;
     // (nor with model-defined invariants, whose pass reads them too)
     if (!nospill && !(verify && (!ckpt.empty() || !recover.empty())) && gpus == 1 &&
-        !(wide && (verify || cont || npred)))
+        !(wide && (verify || cont || npred)) && !ncons)
         c.flags |= RMC_FLAG_SPILL;
+    else if (ncons && !nospill)
+        printf("Note: the constraint pass compacts a resident store: expanded levels do not leave the device "
+               "(-capacity sizes the store).\n");
     c.device_window = window;
     c.set_bytes = fpmem;
     c.seed = fpseed;
@@ -516,6 +544,16 @@ int main(int argc, char** argv) {
         }
         printf("Compiled model-defined invariants:");
         for (int p = 0; p < npred; ++p) printf("%s %s", p ? "," : "", rmc_predicates_name(preds, p));
+        printf("\n");
+    }
+    if (ncons) {
+        if (rmc_set_constraints(ctx, cons)) {
+            printf("Error: %s\n", rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 1;
+        }
+        printf("Compiled %d residual constraint conjunct%s of:", ncons, ncons == 1 ? "" : "s");
+        for (int p = 0; p < ncons; ++p) printf("%s %s", p ? "," : "", rmc_predicates_name(cons, p));
         printf("\n");
     }
     // -gpus N: one ctx per GPU (devices device..device+N-1), each a rank of the
@@ -597,7 +635,7 @@ int main(int argc, char** argv) {
         rc = rmc_run_bfs(ctx, progress, nullptr);
         if (rc) { printf("Error: %s\n", rmc_last_error(ctx)); rmc_destroy(ctx); return 1; }
         rmc_get_result(ctx, &r);
-        if ((r.violated_inv && !cont) || r.deadlock) {  // (-continue: the traces are rmc_trace_violation's)
+        if ((r.violated_inv && !cont) || r.deadlock || rmc_constraint_error(ctx)) {  // (-continue: rmc_trace_violation's)
             size_t len = 0;
             rmc_trace(ctx, nullptr, nullptr, nullptr, 0, &len);
             tr_st.resize(len);
@@ -652,6 +690,13 @@ int main(int argc, char** argv) {
                 print_behaviour();
             }
         }
+        exitcode = 12;
+    } else if (const int ce = gpus == 1 ? rmc_constraint_error(ctx) : 0) {
+        const char* name = rmc_predicates_name(cons, ce - 1);
+        printf("Error: Evaluating constraint %s failed.\n", name ? name : "?");
+        printf("  (residual %d: a read outside its domain — log[i][n] beyond Len(log[i]), a server index that is "
+               "Nil, or a field of another message type)\n", ce - 1);
+        print_behaviour();
         exitcode = 12;
     } else if (r.violated_inv || r.deadlock) {
         if ((uint32_t)r.violated_inv >= RMC_INV_USER0) {  // a model-defined invariant: bit 16 + p
@@ -720,5 +765,6 @@ int main(int argc, char** argv) {
         printf("Finished in %.0fms after recovery (counts include the checkpointed levels)\n", r.seconds * 1e3);
     rmc_destroy(ctx);
     rmc_predicates_free(preds);
+    rmc_predicates_free(cons);
     return exitcode;
 }

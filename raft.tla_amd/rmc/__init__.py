@@ -32,6 +32,7 @@ INV_NAMES = {INV_TYPEOK: "TypeOK", INV_ONE_LEADER: "OneLeaderPerTerm",
              INV_VOTES_GRANTED: "VotesGrantedInv", INV_QUORUM_LOG: "QuorumLogInv",
              INV_MORE_UP_TO_DATE: "MoreUpToDateCorrect", INV_LEADER_COMPLETE: "LeaderCompleteness"}
 FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED, FRONT_PREDICATES = 1, 2, 4, 8
+FRONT_CONSTRAINTS = 16   # RMC_FRONT_CONSTRAINTS: CONSTRAINT conjuncts that are no bound become residuals
 MAX_PREDICATES = 8       # RMC_MAX_PREDICATES: model-defined invariants per program
 INV_USER0 = 1 << 16      # RMC_INV_USER0: predicate p is bit 16 + p of Result.violated_inv
 PRED_HOLDS, PRED_VIOLATED, PRED_ERROR = 0, 1, 2  # verdicts of rmc_eval_predicates
@@ -161,7 +162,8 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_check_states", "rmc_state_keys", "rmc_get_violations", "rmc_trace_violation",
            "rmc_get_levels", "rmc_read_states", "rmc_find_states", "rmc_graph_edges",
            "rmc_predicates_from_files", "rmc_predicates_free", "rmc_predicates_count", "rmc_predicates_name",
-           "rmc_set_predicates", "rmc_eval_predicates", "rmc_predicate_error")
+           "rmc_set_predicates", "rmc_eval_predicates", "rmc_predicate_error",
+           "rmc_constraints_from_files", "rmc_set_constraints", "rmc_constraint_error")
 
 _lib = None
 
@@ -269,6 +271,13 @@ def native():
         lib.rmc_eval_predicates.restype = C.c_int
         lib.rmc_predicate_error.argtypes = [C.c_void_p]
         lib.rmc_predicate_error.restype = C.c_int
+        lib.rmc_constraints_from_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                   C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        lib.rmc_constraints_from_files.restype = C.c_int
+        lib.rmc_set_constraints.argtypes = [C.c_void_p, C.c_void_p]
+        lib.rmc_set_constraints.restype = C.c_int
+        lib.rmc_constraint_error.argtypes = [C.c_void_p]
+        lib.rmc_constraint_error.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -295,14 +304,16 @@ class Predicates:
     INVARIANTs of its .cfg that are none of the ten compiled-in ones, in cfg order.
     `names`: their names; predicate p is bit INV_USER0 << p of Result.violated_inv."""
 
-    def __init__(self, cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False):
+    _from_files = "rmc_predicates_from_files"
+
+    def __init__(self, cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False, options=0):
         self.lib = native()
         self.handle = C.c_void_p()
         err = C.create_string_buffer(4096)
-        opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_DEPTH_BOUNDED if depth_bounded else 0)
-        rc = self.lib.rmc_predicates_from_files(cfg_path.encode(), tla_path.encode() if tla_path else None,
-                                                raft_path.encode() if raft_path else None, opts,
-                                                C.byref(self.handle), err, 4096)
+        opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_DEPTH_BOUNDED if depth_bounded else 0) | options
+        rc = getattr(self.lib, self._from_files)(cfg_path.encode(), tla_path.encode() if tla_path else None,
+                                                 raft_path.encode() if raft_path else None, opts,
+                                                 C.byref(self.handle), err, 4096)
         if rc:
             raise RmcError(rc, err.value.decode())
         self.names = [self.lib.rmc_predicates_name(self.handle, p).decode()
@@ -327,18 +338,32 @@ class Predicates:
         self.close()
 
 
-def load_model(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False, predicates=False):
+class Constraints(Predicates):
+    """The residual conjuncts of a model's CONSTRAINTs, compiled (rmc_constraints_from_files):
+    every top-level conjunct that is none of the four bounds, in order.  `names`: per
+    residual the CONSTRAINT of the .cfg it came from.  Empty: the model has none."""
+    _from_files = "rmc_constraints_from_files"
+
+
+def load_model(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False, predicates=False,
+               constraints=False):
     """(Config, provenance notes, Predicates or None): rmc_model_from_files for a BFS model;
     predicates=True accepts INVARIANTs of the model's own (RMC_FRONT_PREDICATES) and
-    compiles them — hand them to Checker.set_predicates."""
+    compiles them — hand them to Checker.set_predicates.  constraints=True accepts
+    CONSTRAINT conjuncts that are no bound (RMC_FRONT_CONSTRAINTS), compiles them, and
+    returns a fourth value, the Constraints — hand them to Checker.set_constraints."""
     cfg, _sc, notes = model_from_files(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded=depth_bounded,
-                                       predicates=predicates)
-    preds = Predicates(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded) if predicates else None
-    return cfg, notes, preds
+                                       predicates=predicates, constraints=constraints)
+    more = FRONT_CONSTRAINTS if constraints else 0
+    preds = Predicates(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, more) if predicates else None
+    if not constraints:
+        return cfg, notes, preds
+    more = FRONT_PREDICATES if predicates else 0
+    return cfg, notes, preds, Constraints(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, more)
 
 
 def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, simulate=False,
-                     depth_bounded=False, predicates=False):
+                     depth_bounded=False, predicates=False, constraints=False):
     """rmc_model_from_files: (Config, SimConfig or None, provenance notes).
     Raises RmcError naming the construct when the model is not the compiled-in
     raft.tla (with its recognised bug variant, bounds and invariants).
@@ -348,7 +373,8 @@ def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False
     cfg, sc = Config(), SimConfig()
     info = C.create_string_buffer(4096)
     opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_SIMULATE if simulate else 0) | \
-        (FRONT_DEPTH_BOUNDED if depth_bounded else 0) | (FRONT_PREDICATES if predicates else 0)
+        (FRONT_DEPTH_BOUNDED if depth_bounded else 0) | (FRONT_PREDICATES if predicates else 0) | \
+        (FRONT_CONSTRAINTS if constraints else 0)
     rc = lib.rmc_model_from_files(cfg_path.encode(), tla_path.encode() if tla_path else None,
                                   raft_path.encode() if raft_path else None, opts, C.byref(cfg),
                                   C.byref(sc) if simulate else None, info, 4096)
@@ -610,6 +636,16 @@ class Checker:
     def predicate_error(self):
         """rmc_predicate_error: True if the violation run() reported is an evaluation error."""
         return bool(self.lib.rmc_predicate_error(self.ctx))
+
+    # ---- model-defined constraints (rmc.h "model-defined constraints") ----
+    def set_constraints(self, cons):
+        """rmc_set_constraints: run() then keeps only the states on which every compiled
+        residual (a Constraints) holds; None removes them.  The ctx keeps its own copy."""
+        self._check(self.lib.rmc_set_constraints(self.ctx, cons.handle if cons is not None else None))
+
+    def constraint_error(self):
+        """rmc_constraint_error: 1 + the residual whose evaluation error stopped run(), else 0."""
+        return self.lib.rmc_constraint_error(self.ctx)
 
     # ---- the state graph of the last completed run() (rmc.h "state graph export") ----
     def levels(self):

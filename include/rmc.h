@@ -33,7 +33,9 @@ extern "C" {
                               invariants: RMC_FRONT_PREDICATES, rmc_predicates_from_files, rmc_set_predicates,
                               rmc_eval_predicates, rmc_predicate_error, RMC_INV_USER0; 16: model-defined
                               constraints: RMC_FRONT_CONSTRAINTS, rmc_constraints_from_files, rmc_set_constraints,
-                              rmc_constraint_error */
+                              rmc_constraint_error; additive, still 16: action properties: RMC_FRONT_ACTIONS,
+                              rmc_actions_from_files, rmc_set_actions, rmc_eval_actions, rmc_action_violation,
+                              RMC_ACT_USER0, RMC_MAX_ACTION_PROPS */
 
 /* Capacity of the packed encoding (DESIGN.md "Packed state"): the layout the
  * BFS kernels run on when every bound fits it. */
@@ -781,6 +783,57 @@ int rmc_constraints_from_files(const char* cfg_path, const char* tla_path, const
                                uint32_t options, rmc_predicates** out, char* err, size_t err_cap);
 int rmc_set_constraints(rmc_ctx* ctx, const rmc_predicates* p);
 int rmc_constraint_error(const rmc_ctx* ctx);  /* 1 + the residual whose evaluation failed, 0: none */
+
+/* ---- action properties ------------------------------------------------------------------
+ * RMC_FRONT_ACTIONS: a PROPERTY / PROPERTIES name whose definition is [][A]_vars (the
+ * subscript exactly raft.tla's vars) is accepted: a safety property of every transition,
+ * as TLC checks it, with no liveness machinery.  Without the option every PROPERTY stays
+ * refused; every other temporal form (<>, ~>, WF_, SF_, []P of a state predicate, a
+ * conjunction of temporal formulas) is refused by name with or without it.
+ *
+ * A is an expression of the predicate language above plus primes: a primed variable
+ * wherever a state read is accepted (currentTerm'[i], Len(log'[i]), log'[i][n].term,
+ * DOMAIN messages', messages'[m], ...), and a primed parenthesised expression or use of a
+ * definition of the model ((e)', Name', Name(args)'), which primes every variable read
+ * inside; a prime inside a primed expression is refused.  A bound message belongs to the
+ * bag it was bound in (\A m \in DOMAIN messages' binds slots of the successor's bag); using
+ * it to index the other state's bag is refused.  UNCHANGED, ENABLED, \cdot, EXCEPT and
+ * sequence or record equality (log' = log) are refused by name.  At most
+ * RMC_MAX_ACTION_PROPS properties, sharing the predicates' code, stack and bound-name limits.
+ *
+ * rmc_actions_from_files: rmc_model_from_files' arguments; the action properties in cfg
+ * order as an rmc_predicates (rmc_predicates_count / _name / _free apply); count 0: none.
+ * rmc_set_actions copies the program into the ctx (NULL or count 0 removes it).
+ * rmc_run_bfs then evaluates every property, after each expansion launch, on every
+ * transition (s, t) of the launch's parents that the state graph counts as an edge: the
+ * lane is enabled and t satisfies the CONSTRAINT's bounds (stuttering ones included).
+ * [A]_vars is A \/ UNCHANGED vars: "violated" on a transition with t = s is "holds"; an
+ * evaluation error stays an error.  The level is finished first; an invariant (built-in
+ * or model-defined) violated in the same level is reported as without properties;
+ * otherwise the least (source index, lane, property): violated_inv = RMC_ACT_USER0 << p,
+ * violation_depth = the source's level + 1 (the trace's length), rmc_trace = the path to
+ * the source plus the successor (recomputed from the stored source) as the last state
+ * under its family and lane, rmc_action_violation the details.  Counts of a run whose
+ * properties hold equal the run without them; without properties nothing is allocated,
+ * launched or read back.  Single GPU, packed layout; with RMC_FLAG_SPILL, SYMMETRY (stored
+ * representatives to raw successors), VERIFY_STATES, COVERAGE and model-defined invariants.
+ * RMC_E_INVAL: a wide ctx, a sharded ctx (and rmc_shard afterwards), RMC_FLAG_CONTINUE,
+ * constraints set (in either order), under SYMMETRY a property that names a server model
+ * value, a program compiled for another n_servers.  With properties set rmc_simulate,
+ * rmc_checkpoint and rmc_recover are RMC_E_STATE.
+ * rmc_eval_actions (test hook): the same device interpreter on n caller pairs (cur[t],
+ * next[t]), verdicts[t * count + p] for every property with the stutter rule applied.
+ * rmc_action_violation: RMC_E_STATE when the last run reported no action property. */
+#define RMC_FRONT_ACTIONS (1u << 5)
+#define RMC_MAX_ACTION_PROPS 4
+#define RMC_ACT_USER0 (1u << 24) /* property p is bit 24 + p of rmc_result.violated_inv */
+int rmc_actions_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                           uint32_t options, rmc_predicates** out, char* err, size_t err_cap);
+int rmc_set_actions(rmc_ctx* ctx, const rmc_predicates* p);
+int rmc_eval_actions(rmc_ctx* ctx, const rmc_state_view* cur, const rmc_state_view* next, size_t n,
+                     uint8_t* verdicts);
+int rmc_action_violation(const rmc_ctx* ctx, int32_t* property, uint64_t* src_index, int32_t* family,
+                         int32_t* instance, int32_t* is_error);
 
 /* rmc_model_from_files for BFS / simulation models with raft_path = NULL and
  * RMC_FRONT_BUILTIN_RAFT taken from the environment (RMC_BUILTIN_RAFT=1).

@@ -261,6 +261,8 @@ int end_level(rmc_ctx* c, u64 hi, int* depth, rmc_progress_fn cb, void* user,
         if (int rc = pred_scan(c, *depth)) return rc;
     if (cons_on(c))  // (the level's kept states: [hi, count))
         if (int rc = cons_scan(c, *depth, hi)) return rc;
+    if (act_on(c))  // (last: an invariant violated in the level wins)
+        if (int rc = act_scan(c)) return rc;
     if (cb) {
         rmc_level_stats ls{};
         ls.level = nnew ? *depth - 1 : *depth;
@@ -457,6 +459,7 @@ void rmc_destroy(rmc_ctx* c) {
     (void)hipFree(c->d_viol);
     pred_free(c);
     cons_free(c);
+    act_free(c);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -488,6 +491,8 @@ static int start_run(rmc_ctx* c, int* depth) {
         if (int rc = pred_begin(c)) return rc;
     if (cons_on(c))
         if (int rc = cons_begin(c)) return rc;
+    if (act_on(c))
+        if (int rc = act_begin(c)) return rc;
     c->B.vlo = 0;
     c->spill.hcopied = 0;
     c->spill.host_hits = 0;
@@ -520,6 +525,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     // the state graph calls (rmc_graph.cpp) read a completed run only: its index is built on demand
     c->run_done = 0;
     c->run_cons = cons_on(c) ? 1 : 0;
+    c->act_hit = 0;
     c->graph_idx = 0;
     c->run_seed = c->cfg.seed;
     if (c->wide || c->dist.on) {
@@ -538,6 +544,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
     const bool cont = continue_on(c);
     const bool preds = pred_on(c);  // (rmc_recover refuses a ctx with predicates too)
     const bool cons = cons_on(c);   // (and one with constraints)
+    const bool acts = act_on(c);    // (and one with action properties; never with cons: rmc_set_actions)
     int depth = 0;
     if (resume) {
         c->res.left_on_queue = 0;
@@ -672,7 +679,7 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                         c->res.spills = cnt / win;  // passes of the ring
                     }
                 }
-                if (cover || cont || preds || cons) {
+                if (cover || cont || preds || cons || acts) {
                     // the coverage pass of this launch: its parents [a, b) are still resident
                     // (the store; the linear window, which moves only [base, a) and before the
                     // launch; the ring, whose room is relative to a: a launch stopped on
@@ -694,6 +701,10 @@ int rmc_run_bfs(rmc_ctx* c, rmc_progress_fn cb, void* user) {
                     if (cont) HIPCHK(c, c->k->violations(c->P, c->B, cov_before, c->h_ctr->count, c->d_viol, c->st));
                     if (preds)
                         if (int rc = pred_pass(c, cov_before, c->h_ctr->count)) return rc;
+                    // the action properties: the launch's parents, as coverage walks them (a
+                    // launch stopped on admission checks all its parents here, its re-launches none)
+                    if (acts)
+                        if (int rc = act_pass(c, resumed ? b : a, b)) return rc;
                 }
                 // a launch that stopped on admission left units unclaimed (every claimed one is
                 // finished): again over [a, b), live from the first window not fully claimed
@@ -791,7 +802,7 @@ int rmc_get_result(const rmc_ctx* c, rmc_result* out) {
 // recorded lanes from the last state still known (Init at worst) with the listing
 // kernel — the stored successor of a parent through a lane is exactly what it lists.
 static int trace_to(rmc_ctx* c, u64 target, rmc_state_view* states, int32_t* families, int32_t* instances, size_t cap,
-                    size_t* len) {
+                    size_t* len, std::vector<u32>* last = nullptr) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->wide) return trace_wide(c, target, states, families, instances, cap, len);
     std::vector<u64> chain;
@@ -837,6 +848,7 @@ static int trace_to(rmc_ctx* c, u64 target, rmc_state_view* states, int32_t* fam
             fill_step(families, instances, q, family_of(c->P, acts[q]), acts[q]);
         }
     }
+    if (last) *last = cur;  // the target's packed words
     return 0;
 }
 
@@ -848,6 +860,19 @@ int rmc_trace(rmc_ctx* c, rmc_state_view* states, int32_t* families, int32_t* in
     if (c->dist.on && !c->wide) {
         HIPCHK(c, hipSetDevice(c->cfg.device));
         return trace_sharded(c, states, families, instances, cap, len);
+    }
+    if (c->act_hit) {
+        // an action property: the path to the source, then the violating transition's successor,
+        // recomputed from the stored source through the lane code
+        std::vector<u32> src, nxt((size_t)c->NW);
+        if (int rc = trace_to(c, c->target_idx, states, families, instances, cap, len, &src)) return rc;
+        if (int rc = act_successor(c, src.data(), c->act_lane, nxt.data())) return rc;
+        const size_t q = (*len)++;
+        if (q < cap) {
+            if (states) decode_state(c->sh.S, c->sh.K, nxt.data(), &states[q]);
+            fill_step(families, instances, q, family_of(c->P, c->act_lane), (uint8_t)c->act_lane);
+        }
+        return 0;
     }
     return trace_to(c, c->target_idx, states, families, instances, cap, len);
 }
@@ -882,6 +907,9 @@ int run_sim(rmc_ctx* c, const rmc_sim_config* sc, rmc_sim_result* out, i64 rec_b
     if (cons_on(c))
         return fail(c, RMC_E_STATE, "simulation does not evaluate model-defined constraints (rmc_set_constraints(ctx, "
                                     "NULL) removes them)");
+    if (act_on(c))
+        return fail(c, RMC_E_STATE, "simulation does not evaluate action properties (rmc_set_actions(ctx, NULL) removes "
+                                    "them)");
     if (c->wide) return sim_wide(c, sc, out, rec_beh, wrec);
     if (sc->mode == RMC_SIM_TLC)
         return fail(c, RMC_E_INVAL, "RMC_SIM_TLC draws on the wide layout only (bounds beyond the packed capacity)");

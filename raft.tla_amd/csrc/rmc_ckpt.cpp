@@ -79,6 +79,8 @@ int rmc_checkpoint(rmc_ctx* c, const char* path) {
         return fail(c, RMC_E_STATE, "checkpoint: not supported with model-defined invariants set (rmc_set_predicates)");
     if (cons_on(c))
         return fail(c, RMC_E_STATE, "checkpoint: not supported with model-defined constraints set (rmc_set_constraints)");
+    if (act_on(c))
+        return fail(c, RMC_E_STATE, "checkpoint: not supported with action properties set (rmc_set_actions)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "checkpoint: not supported with RMC_FLAG_COVERAGE (the tallies are of whole "
                                     "runs and are not written)");
@@ -142,6 +144,9 @@ int rmc_recover(rmc_ctx* c, const char* path) {
     if (cons_on(c))
         return fail(c, RMC_E_STATE, "recover: not supported with model-defined constraints set (rmc_set_constraints): "
                                     "recovery rebuilds the set from the stored states, without the removed ones' keys");
+    if (act_on(c))
+        return fail(c, RMC_E_STATE, "recover: not supported with action properties set (rmc_set_actions): the levels "
+                                    "before the checkpoint were expanded without them");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_STATE, "recover: not supported with RMC_FLAG_COVERAGE (the tallies are of whole runs)");
     if (c->cfg.flags & RMC_FLAG_CONTINUE)

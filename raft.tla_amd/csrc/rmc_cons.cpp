@@ -150,6 +150,9 @@ int rmc_set_constraints(rmc_ctx* c, const rmc_predicates* p) {
         return fail(c, RMC_E_INVAL, "rmc_set_constraints: model-defined constraints run on the packed layout (this "
                                     "model's bounds need the wide layout)");
     if (c->dist.on) return fail(c, RMC_E_INVAL, "rmc_set_constraints: model-defined constraints are single-GPU (the ctx is sharded)");
+    if (act_on(c))
+        return fail(c, RMC_E_INVAL, "rmc_set_constraints: action properties are set (rmc_set_actions): their pass checks "
+                                    "the transitions the bounds admit, before a residual removes any");
     if ((f & RMC_FLAG_SYMMETRY) && p->names_server)
         return fail(c, RMC_E_INVAL, "rmc_set_constraints: a residual names a server model value, so it is not "
                                     "invariant under SYMMETRY Permutations(Server)");

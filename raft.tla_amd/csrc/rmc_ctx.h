@@ -163,6 +163,16 @@ struct rmc_ctx {
     rmc::pred::Program* d_prog = nullptr;
     unsigned long long* d_pword = nullptr;
     int pred_error = 0;
+    // action properties (rmc_set_actions; rmc_act.cpp, rmc_dev_act.h): the ctx's copy of the program and
+    // its names, the program in device memory and the pass's word (min over the failing transitions
+    // of source << 16 | lane << 8 | property << 1 | error), all allocated by rmc_set_actions only; and
+    // the last run's reported transition (act_hit: rmc_action_violation, and rmc_trace's last state)
+    rmc_predicates* acts = nullptr;
+    rmc::pred::Program* d_aprog = nullptr;
+    rmc::Params* d_apar = nullptr;  // the run's Params in device memory (act_begin)
+    unsigned long long* d_aword = nullptr;
+    int act_hit = 0, act_prop = 0, act_lane = 0, act_error = 0;
+    rmc::u64 act_src = 0;
     // model-defined constraints (rmc_set_constraints; rmc_cons.cpp, rmc_dev_cons.h): the ctx's copy of
     // the residuals' program and names, the program in device memory, the pass's word (min over the
     // states a residual's evaluation failed on), its scratch for launches of up to cons_cap new states
@@ -260,6 +270,17 @@ void pred_free(rmc_ctx* c);
 // pred_scan) the word read back: an evaluation error stops the search, the target the least kept
 // state of the level [level_lo, count) on which a residual's evaluation fails.
 inline bool cons_on(const rmc_ctx* c) { return c->cons != nullptr; }
+// Action properties (packed layout, single GPU): the word cleared at the start of a run; the pass
+// over a launch's parents [lo, hi), still resident; at a level's end (after the invariants' scans)
+// the word read back: it is the target only when no invariant is violated in the level.  act_tail:
+// the reported transition's successor, recomputed on the host from the stored source `src` (NW
+// words) through the lane code.
+inline bool act_on(const rmc_ctx* c) { return c->acts != nullptr; }
+int act_begin(rmc_ctx* c);
+int act_pass(rmc_ctx* c, rmc::u64 lo, rmc::u64 hi);
+int act_scan(rmc_ctx* c);
+void act_free(rmc_ctx* c);
+int act_successor(rmc_ctx* c, const rmc::u32* src, int lane, rmc::u32* out);
 // The Params of the seed and expansion launches.
 inline const rmc::Params& expand_params(const rmc_ctx* c) { return c->cons ? c->PE : c->P; }
 int cons_begin(rmc_ctx* c);

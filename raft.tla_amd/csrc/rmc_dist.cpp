@@ -659,6 +659,9 @@ int rmc_shard(rmc_ctx* c, int32_t rank, int32_t world, const uint8_t* rccl_id, c
     if (cons_on(c))
         return fail(c, RMC_E_INVAL, "rmc_shard: model-defined constraints are single-GPU (rmc_set_constraints(ctx, NULL) "
                                     "removes them)");
+    if (act_on(c))
+        return fail(c, RMC_E_INVAL, "rmc_shard: action properties are single-GPU (rmc_set_actions(ctx, NULL) removes "
+                                    "them)");
     if (c->cfg.flags & RMC_FLAG_COVERAGE)
         return fail(c, RMC_E_INVAL, "sharded mode does not support RMC_FLAG_COVERAGE (coverage is single GPU)");
     if (c->cfg.flags & RMC_FLAG_CONTINUE)

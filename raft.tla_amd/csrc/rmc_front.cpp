@@ -594,9 +594,12 @@ void set_min(int* dst, int v) { *dst = (*dst < 0 || v < *dst) ? v : *dst; }
 // compile those into it (rmc_predicates_from_files).  RMC_FRONT_CONSTRAINTS (16) record the
 // CONSTRAINT conjuncts that are no bound as residuals.  cons != nullptr: compile those
 // into it (rmc_constraints_from_files).
+// RMC_FRONT_ACTIONS (32) accept a PROPERTY of the form [][A]_vars.  acts != nullptr: compile those
+// into it (rmc_actions_from_files).
 static int parse_model(const char* cfg_path, const char* tla_path, const char* raft_path, uint32_t options,
                        rmc_config* out, rmc_sim_config* sim, char* info, size_t info_cap,
-                       rmc_predicates* preds = nullptr, rmc_predicates* cons = nullptr) {
+                       rmc_predicates* preds = nullptr, rmc_predicates* cons = nullptr,
+                       rmc_predicates* acts = nullptr) {
     std::string e;
     auto fail = [&](const std::string& m) {
         if (info && info_cap) snprintf(info, info_cap, "%s", m.c_str());
@@ -754,7 +757,55 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
     } else if (C.subst.count("Init")) {
         return fail("Init overrides (e.g. Smokeraft's SmokeInit) are simulation models (rmc-tlc -simulate)");
     }
-    if (!C.props.empty()) return fail("PROPERTY " + C.props[0] + " (liveness) is out of scope");
+    // ---- PROPERTY: [][A]_vars is a safety property of every transition (an action property);
+    // every other temporal form needs liveness checking
+    std::vector<ActionProp> action_props;
+    if (!C.props.empty() && !(options & RMC_FRONT_ACTIONS))
+        return fail("PROPERTY " + C.props[0] + " (liveness) is out of scope");
+    for (const auto& pn : C.props) {
+        const Unit* u = X.def(pn);
+        if (!u) return fail("PROPERTY " + pn + " is not defined by the model");
+        const std::vector<Tok> bt = tokenize(*u, true);
+        auto at = [](const Tok& t) { return " at line " + std::to_string(t.line) + ", col " + std::to_string(t.col); };
+        for (size_t k = 0; k < bt.size(); ++k) {
+            const std::string& t = bt[k].t;
+            const char* what = t == "<>" ? "<> (eventually)" : t == "~>" ? "~> (leads to)"
+                               : t.rfind("WF_", 0) == 0 ? "WF_ (weak fairness)" : t.rfind("SF_", 0) == 0 ? "SF_ (strong fairness)"
+                               : nullptr;
+            if (what)
+                return fail("PROPERTY " + pn + ": " + what + at(bt[k]) + " needs liveness checking, which is out of scope "
+                            "(a PROPERTY must be [][A]_vars)");
+        }
+        if (bt.size() < 2 || bt[0].t != "[]")
+            return fail("PROPERTY " + pn + " is not of the form [][A]_vars" + (bt.empty() ? "" : at(bt[0])));
+        if (bt[1].t != "[")
+            return fail("PROPERTY " + pn + ": [] applied to a state predicate" + at(bt[0]) + " is a temporal formula "
+                        "(liveness checking is out of scope; state it as an INVARIANT, or as [][A]_vars)");
+        size_t close = 0;
+        int d = 0;
+        for (size_t k = 1; k < bt.size(); ++k) {
+            if (bt[k].t == "[") ++d;
+            if (bt[k].t == "]" && --d == 0) { close = k; break; }
+        }
+        if (!close) return fail("PROPERTY " + pn + ": `[` without its `]`" + at(bt[1]));
+        if (close + 1 >= bt.size() || bt[close + 1].t[0] != '_')
+            return fail("PROPERTY " + pn + ": expected the subscript _vars after `]`" + at(bt[close]));
+        if (bt[close + 1].t != "_vars" || (close + 2 < bt.size() && bt[close + 2].t != "/\\" && bt[close + 2].t != "\\land")) {
+            std::string sub = bt[close + 1].t.substr(1);
+            for (size_t k = close + 2; k < bt.size() && bt[k].t != "/\\" && bt[k].t != "\\land"; ++k) sub += bt[k].t;
+            return fail("PROPERTY " + pn + ": the subscript " + sub + at(bt[close + 1]) + " is not raft.tla's vars "
+                        "(an action property is [][A]_vars)");
+        }
+        if (close + 2 < bt.size())
+            return fail("PROPERTY " + pn + ": a conjunction of temporal formulas" + at(bt[close + 2]) + " (name each "
+                        "[][A]_vars as a PROPERTY of its own; liveness checking is out of scope)");
+        if (close == 2) return fail("PROPERTY " + pn + ": [][A]_vars with an empty A" + at(bt[1]));
+        ActionProp ap;
+        ap.name = pn;
+        ap.toks.assign(bt.begin() + 2, bt.begin() + (long)close);
+        action_props.push_back(ap);
+        notes.push_back("PROPERTY " + pn + ": action property [][A]_vars, checked on every transition");
+    }
     if (!C.unknown.empty()) return fail("cfg section " + C.unknown[0] + " is not supported");
     // ---- overrides
     for (auto& kv : C.subst) {
@@ -995,6 +1046,10 @@ static int parse_model(const char* cfg_path, const char* tla_path, const char* r
         std::string why;
         if (!compile_residuals(X, residuals, server_elems, elems, cons, &why)) return fail(why);
     }
+    if (acts) {
+        std::string why;
+        if (!compile_actions(X, action_props, server_elems, elems, acts, &why)) return fail(why);
+    }
     *out = g;
     if (info && info_cap) {
         std::string all;
@@ -1045,6 +1100,24 @@ extern "C" int rmc_constraints_from_files(const char* cfg_path, const char* tla_
     rmc_sim_config sim;
     if (int rc = parse_model(cfg_path, tla_path, raft_path, options | RMC_FRONT_CONSTRAINTS, &cfg, &sim, err, err_cap,
                              nullptr, p.get()))
+        return rc;
+    if (err && err_cap) err[0] = 0;
+    *out = p.release();
+    return 0;
+}
+
+extern "C" int rmc_actions_from_files(const char* cfg_path, const char* tla_path, const char* raft_path,
+                                      uint32_t options, rmc_predicates** out, char* err, size_t err_cap) {
+    if (!out) {
+        if (err && err_cap) snprintf(err, err_cap, "null argument");
+        return RMC_E_PARSE;
+    }
+    *out = nullptr;
+    std::unique_ptr<rmc_predicates> p(new rmc_predicates());
+    rmc_config cfg;
+    rmc_sim_config sim;
+    if (int rc = parse_model(cfg_path, tla_path, raft_path, options | RMC_FRONT_ACTIONS, &cfg, &sim, err, err_cap,
+                             nullptr, nullptr, p.get()))
         return rc;
     if (err && err_cap) err[0] = 0;
     *out = p.release();

@@ -189,6 +189,14 @@ struct ShapeKernels {
     hipError_t (*pred)(const pred::Program* prog, const DevBufs& B, u64 nlo, u64 nhi, unsigned long long* word,
                        hipStream_t st);
     hipError_t (*pred_eval)(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st);
+    // action properties (k_act, k_act_eval, rmc_dev_act.h): the transitions out of a launch's parents
+    // [lo, hi) that are edges of the state graph, into word = min (source << 16 | lane << 8 |
+    // property << 1 | error) over those a property does not hold on; out[t * n_pred + p] = property
+    // p's verdict on the pair in[t] (the current state's words, then the next state's).  P: the
+    // model's parameters in device memory (the kernel keeps them in LDS)
+    hipError_t (*act)(const pred::Program* prog, const Params* P, const DevBufs& B, u64 lo, u64 hi,
+                      unsigned long long* word, hipStream_t st);
+    hipError_t (*act_eval)(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st);
     // model-defined constraints (rmc_dev_cons.h; prog: the residuals' program in device memory): the
     // states a launch added, [nlo, nhi), filtered and compacted in place — afterwards [nlo, nlo + kept)
     // holds the kept states with their links and Counters.count = nlo + kept; word = min (index << 8 |

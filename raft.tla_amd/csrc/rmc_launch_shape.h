@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "rmc_dev_act.h"
 #include "rmc_dev_cons.h"
 #include "rmc_dev_expand.h"
 #include "rmc_dev_graph.h"
@@ -86,6 +87,25 @@ template <int S, int K>
 static hipError_t launch_pred_eval_t(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL((k_pred_eval<S, K>), dim3((unsigned)((n + kPredThreads - 1) / kPredThreads)), dim3(kPredThreads),
+                       0, st, prog, in, n, out);
+    return hipGetLastError();
+}
+
+// The action-property pass of one expansion launch over its parents [lo, hi).
+template <int S, int K>
+static hipError_t launch_act_t(const pred::Program* prog, const Params* P, const DevBufs& B, u64 lo, u64 hi,
+                               unsigned long long* word, hipStream_t st) {
+    if (hi <= lo) return hipSuccess;
+    const u64 blocks = (hi - lo + kPredThreads - 1) / kPredThreads;
+    hipLaunchKernelGGL((k_act<S, K>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kPredThreads), 0, st, prog,
+                       P, B, lo, hi, word);
+    return hipGetLastError();
+}
+
+template <int S, int K>
+static hipError_t launch_act_eval_t(const pred::Program* prog, const u32* in, u64 n, uint8_t* out, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL((k_act_eval<S, K>), dim3((unsigned)((n + kPredThreads - 1) / kPredThreads)), dim3(kPredThreads),
                        0, st, prog, in, n, out);
     return hipGetLastError();
 }
@@ -320,6 +340,8 @@ static ShapeKernels shape_table() {
     k.check = launch_check_t<S, K>;
     k.pred = launch_pred_t<S, K>;
     k.pred_eval = launch_pred_eval_t<S, K>;
+    k.act = launch_act_t<S, K>;
+    k.act_eval = launch_act_eval_t<S, K>;
     k.cons = launch_cons_t<S, K>;
     k.cons_inv = launch_cons_inv_t<S, K>;
     k.keys = launch_keys_t<S, K>;

@@ -72,7 +72,7 @@ int rmc_set_predicates(rmc_ctx* c, const rmc_predicates* p) {
         return 0;
     }
     const pred::Program& g = p->prog;
-    if (g.n_pred < 0 || g.n_pred > pred::PRED_MAX || g.n_code < 1 || g.n_code > pred::PRED_CODE)
+    if (p->actions || g.n_pred < 0 || g.n_pred > pred::PRED_MAX || g.n_code < 1 || g.n_code > pred::PRED_CODE)
         return fail(c, RMC_E_INVAL, "rmc_set_predicates: not a program of rmc_predicates_from_files");
     if (continue_on(c))
         return fail(c, RMC_E_INVAL, "rmc_set_predicates: a ctx with RMC_FLAG_CONTINUE counts the ten compiled-in "
@@ -97,7 +97,10 @@ int rmc_set_predicates(rmc_ctx* c, const rmc_predicates* p) {
     return 0;
 }
 
-int rmc_predicate_error(const rmc_ctx* c) { return c && c->res.violated_inv >= (int32_t)RMC_INV_USER0 ? c->pred_error : 0; }
+int rmc_predicate_error(const rmc_ctx* c) {
+    return c && c->res.violated_inv >= (int32_t)RMC_INV_USER0 && c->res.violated_inv < (int32_t)RMC_ACT_USER0 ? c->pred_error
+                                                                                                             : 0;
+}
 
 int rmc_eval_predicates(rmc_ctx* c, const rmc_state_view* states, size_t n, uint8_t* verdicts) {
     if (!c) return RMC_E_INVAL;

@@ -19,6 +19,9 @@
 // stride of its working memory, PRED_ROWS words per evaluation: the device kernels keep
 // it in LDS columns (stride = the block's threads; each thread its own column, so no
 // barrier and no bank conflict), the host in a local array (stride 1).
+//
+// An action property (PROPERTY [][A]_vars) is a program over two states: run2 takes a
+// current and a next accessor, and a read flagged OP_PRIMED reads the next one.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -98,6 +101,10 @@ RMC_HD int field_type(int f) {
            : f < F_MSUCCESS ? (int)AEQ : (int)AEP;
 }
 
+// An action property's read of the next state: the state-read operation with this bit (bit 7 of
+// the operation byte; the operations stay below 128).  Programs without primes hold none.
+constexpr u32 OP_PRIMED = 128u;
+
 constexpr u32 ins(Op op, int arg = 0) { return (u32)op | ((u32)arg << 8); }
 RMC_HD u32 ins_op(u32 w) { return w & 255u; }
 RMC_HD int ins_arg(u32 w) { return (int)w >> 8; }
@@ -105,11 +112,13 @@ RMC_HD int ins_arg(u32 w) { return (int)w >> 8; }
 // ---- state accessors: every read an int ----------------------------------------------
 // The packed state in place: (2 S + K) 32-bit words (raft_packed.h), read where they lie
 // (the store, a staged array), so no thread holds a dynamically indexed copy.
-template <int S, int K>
+// STRIDE: the distance between its words (1: a record; a block's threads: a thread's LDS column,
+// rmc_dev_act.h).
+template <int S, int K, int STRIDE = 1>
 struct PackedAcc {
     const u32* r;
-    RMC_HD u64 w(int i) const { return (u64)r[2 * i] | ((u64)r[2 * i + 1] << 32); }
-    RMC_HD u32 m(int q) const { return r[2 * S + q]; }
+    RMC_HD u64 w(int i) const { return (u64)r[(2 * i) * STRIDE] | ((u64)r[(2 * i + 1) * STRIDE] << 32); }
+    RMC_HD u32 m(int q) const { return r[(2 * S + q) * STRIDE]; }
     RMC_HD int servers() const { return S; }
     RMC_HD int term(int i) const { return (int)w_ct(w(i)); }
     RMC_HD int role(int i) const { return (int)w_st(w(i)); }
@@ -224,8 +233,11 @@ struct ViewAcc {
 // ---- the interpreter --------------------------------------------------------------------
 // One predicate from code[pc] on: 0 it holds, 1 it is violated, 2 an evaluation error.
 // mem: PRED_ROWS words at stride STRIDE (row k at mem[k * STRIDE]).
-template <int STRIDE, class Acc>
-RMC_HD int run(const u32* code, int pc, const Acc& a, int* mem) {
+// PRIMED (action properties, DESIGN.md "Action properties"): a state read whose operation carries
+// OP_PRIMED reads the next state `n`; without PRIMED the code holds no such operation and `n` is not
+// looked at (the one-state entry point below passes the current state twice).
+template <int STRIDE, bool PRIMED, class Acc, class AccN>
+RMC_HD int run2(const u32* code, int pc, const Acc& a, const AccN& n, int* mem) {
 #define PR_STK(k) mem[(k) * STRIDE]
 #define PR_VAL(r) mem[(PRED_STACK + 2 * (r)) * STRIDE]
 #define PR_AUX(r) mem[(PRED_STACK + 2 * (r) + 1) * STRIDE]
@@ -234,7 +246,10 @@ RMC_HD int run(const u32* code, int pc, const Acc& a, int* mem) {
     for (;;) {
         const u32 w = code[pc++];
         const int arg = ins_arg(w);
-        switch (ins_op(w)) {
+        const bool pr = PRIMED && (w & OP_PRIMED) != 0;
+#define PR_RD(call) (PRIMED && pr ? n.call : a.call)
+        const u32 op = PRIMED ? (w & (OP_PRIMED - 1u)) : ins_op(w);
+        switch (op) {
             case OP_HALT: return PR_STK(sp - 1) ? 0 : 1;
             case OP_PUSH: PR_STK(sp++) = arg; break;
             case OP_LOAD: PR_STK(sp++) = PR_VAL(arg); break;
@@ -291,43 +306,43 @@ RMC_HD int run(const u32* code, int pc, const Acc& a, int* mem) {
         PR_STK(sp - 1) = (read);          \
     }                                     \
     break
-            case OP_TERM: PR_SRV(a.term(i));
-            case OP_ROLE: PR_SRV(a.role(i));
-            case OP_VOTED: PR_SRV(a.voted(i));
-            case OP_COMMIT: PR_SRV(a.commit(i));
-            case OP_VRESP: PR_SRV(a.vresp(i));
-            case OP_VGRANT: PR_SRV(a.vgrant(i));
-            case OP_LEN: PR_SRV(a.len(i));
-            case OP_LASTTERM: PR_SRV(a.len(i) ? a.log_term(i, a.len(i) - 1) : 0);
+            case OP_TERM: PR_SRV(PR_RD(term(i)));
+            case OP_ROLE: PR_SRV(PR_RD(role(i)));
+            case OP_VOTED: PR_SRV(PR_RD(voted(i)));
+            case OP_COMMIT: PR_SRV(PR_RD(commit(i)));
+            case OP_VRESP: PR_SRV(PR_RD(vresp(i)));
+            case OP_VGRANT: PR_SRV(PR_RD(vgrant(i)));
+            case OP_LEN: PR_SRV(PR_RD(len(i)));
+            case OP_LASTTERM: PR_SRV(PR_RD(len(i)) ? PR_RD(log_term(i, PR_RD(len(i)) - 1)) : 0);
 #undef PR_SRV
             case OP_NEXT:
             case OP_MATCH: {
                 const int j = PR_STK(--sp), i = PR_STK(sp - 1);
                 if (i < 0 || i >= S || j < 0 || j >= S) return 2;
-                PR_STK(sp - 1) = ins_op(w) == OP_NEXT ? a.next(i, j) : a.match(i, j);
+                PR_STK(sp - 1) = op == OP_NEXT ? PR_RD(next(i, j)) : PR_RD(match(i, j));
                 break;
             }
             case OP_LOGTERM:
             case OP_LOGVAL: {
-                const int n = PR_STK(--sp), i = PR_STK(sp - 1);
+                const int k = PR_STK(--sp), i = PR_STK(sp - 1);
                 if (i < 0 || i >= S) return 2;
-                if (n < 1 || n > a.len(i)) return 2;
-                PR_STK(sp - 1) = ins_op(w) == OP_LOGTERM ? a.log_term(i, n - 1) : a.log_val(i, n - 1);
+                if (k < 1 || k > PR_RD(len(i))) return 2;
+                PR_STK(sp - 1) = op == OP_LOGTERM ? PR_RD(log_term(i, k - 1)) : PR_RD(log_val(i, k - 1));
                 break;
             }
-            case OP_NMSG: PR_STK(sp++) = a.nmsg(); break;
+            case OP_NMSG: PR_STK(sp++) = PR_RD(nmsg()); break;
             case OP_MSGCNT: {
                 const int q = PR_STK(sp - 1);
-                if (q < 0 || q >= a.nmsg()) return 2;
-                PR_STK(sp - 1) = a.msg_cnt(q);
+                if (q < 0 || q >= PR_RD(nmsg())) return 2;
+                PR_STK(sp - 1) = PR_RD(msg_cnt(q));
                 break;
             }
             case OP_MSGF: {
                 const int q = PR_STK(sp - 1);
-                if (q < 0 || q >= a.nmsg()) return 2;
+                if (q < 0 || q >= PR_RD(nmsg())) return 2;
                 const int ft = field_type(arg);
-                if (ft >= 0 && a.msg_field(q, F_MTYPE) != ft) return 2;
-                PR_STK(sp - 1) = a.msg_field(q, arg);
+                if (ft >= 0 && PR_RD(msg_field(q, F_MTYPE)) != ft) return 2;
+                PR_STK(sp - 1) = PR_RD(msg_field(q, arg));
                 break;
             }
             case OP_ITER_RANGE: {
@@ -374,6 +389,13 @@ RMC_HD int run(const u32* code, int pc, const Acc& a, int* mem) {
 #undef PR_STK
 #undef PR_VAL
 #undef PR_AUX
+#undef PR_RD
+}
+
+// One state predicate (an INVARIANT, a CONSTRAINT's residual): no primed reads.
+template <int STRIDE, class Acc>
+RMC_HD int run(const u32* code, int pc, const Acc& a, int* mem) {
+    return run2<STRIDE, false>(code, pc, a, a, mem);
 }
 
 // Every predicate in order: 0 if all hold, else 1 + (p << 1 | error) of the first that
@@ -396,4 +418,5 @@ struct rmc_predicates {
     rmc::pred::Program prog;
     char name[RMC_MAX_PREDICATES][64];
     int names_server;
+    int actions;  // action properties (rmc_actions_from_files): two-state programs, for rmc_set_actions only
 };

@@ -10,11 +10,17 @@
 // definitions in place, and emits code while it tracks the stack depth, the bound names
 // in scope and the code size — the bounds the interpreter relies on.  Whatever is not in
 // the language is refused by name, with its line and column.
+//
+// An action property's body (PROPERTY [][A]_vars, compile_actions; DESIGN.md "Action
+// properties") is the same language plus primes: the parser accepts x', (e)', Name' and
+// Name(args)' as a PRIME node, and the generator emits the successor's state reads
+// (OP_PRIMED) for a primed variable and for every read inside a primed expression.  A
+// bound message remembers the bag it was bound in.  Without primes nothing changes.
 
 struct PNode;
 typedef std::shared_ptr<PNode> PNodeP;
 struct PNode {
-    enum Kind { NUM, ID, INDEX, CALL, FIELD, NOT, BIN, IF, QUANT, SETLIT, SETCOMP, DOMAIN, RANGE } kind;
+    enum Kind { NUM, ID, INDEX, CALL, FIELD, NOT, BIN, IF, QUANT, SETLIT, SETCOMP, DOMAIN, RANGE, PRIME } kind;
     std::string s;  // NUM: digits; ID / CALL / FIELD: the name; BIN: the operator; QUANT: \A or \E; SETCOMP: the bound name
     int line = 0, col = 0;
     std::vector<PNodeP> k;
@@ -31,6 +37,7 @@ class PredParser {
     const std::vector<Tok>& v;
     size_t i = 0;
     std::vector<int> margin;  // bullet columns of the open junction lists
+    bool primes;              // an action property's body: x', (e)', Name', Name(args)' are accepted
 
     const Tok* peek() const {
         if (i >= v.size()) return nullptr;
@@ -72,7 +79,7 @@ class PredParser {
     static bool ident_tok(const std::string& t) { return !t.empty() && (isalpha((unsigned char)t[0]) || t[0] == '_'); }
 
 public:
-    explicit PredParser(const std::vector<Tok>& toks) : v(toks) {}
+    explicit PredParser(const std::vector<Tok>& toks, bool accept_primes = false) : v(toks), primes(accept_primes) {}
 
     PNodeP parse_all() {
         if (v.empty()) throw PredError{"the definition is empty"};
@@ -177,7 +184,11 @@ public:
                 n->k = {a};
                 a = n;
             } else if (is("'")) {
-                refuse("a primed variable (a state predicate reads one state)", peek());
+                if (!primes) refuse("a primed variable (a state predicate reads one state)", peek());
+                const Tok op = v[i++];
+                PNodeP n = node(PNode::PRIME, op);
+                n->k = {a};
+                a = n;
             } else {
                 return a;
             }
@@ -336,6 +347,7 @@ struct PEnv;
 struct PBinding {
     int reg = -1;   // a bound name's register, or -1: a definition's parameter
     PTy ty = T_INT;
+    bool bagp = false;  // a bound message: a slot of the successor's bag (\A m \in DOMAIN messages')
     PNodeP arg;     // parameter: the argument, generated in the caller's scope
     const PEnv* env = nullptr;
 };
@@ -359,6 +371,17 @@ class PredGen {
     int depth = 0, max_depth = 0, nreg = 0, max_reg = 0;
     std::vector<std::string> expanding;
     using Op = rmc::pred::Op;
+    bool actions = false;  // an action property's body: primes are in the language
+    bool msg_bagp = false;  // the bag of the bound message loaded last (gen_id)
+    bool primed = false;   // inside a primed expression: every state read is of the successor
+    // a state read of the state the expression is in (or of the successor: a primed variable)
+    static Op rd(Op op, bool next) { return (Op)((uint32_t)op | (next ? rmc::pred::OP_PRIMED : 0u)); }
+    struct PrimeScope {  // primes what is generated while it lives
+        PredGen& g;
+        bool was;
+        PrimeScope(PredGen& gen, bool on) : g(gen), was(gen.primed) { g.primed = was || on; }
+        ~PrimeScope() { g.primed = was; }
+    };
 
 public:
     int names_server = 0;
@@ -368,6 +391,7 @@ public:
         : X(x), servers(sv), values(vv), code(out) {}
     int stack_depth() const { return max_depth; }
     int bound_names() const { return max_reg; }
+    void set_actions(bool on) { actions = on; }
 
     void predicate(const std::string& name) {
         PEnv top;
@@ -380,7 +404,8 @@ public:
     void residual(const std::vector<Tok>& toks) {
         PEnv top;
         depth = 0;
-        const PTy t = gen(PredParser(toks).parse_all(), top);
+        primed = false;
+        const PTy t = gen(PredParser(toks, actions).parse_all(), top);
         if (t != T_BOOL) throw PredError{"the conjunct is not Boolean (it is a " + std::string(ty_name(t)) + ")"};
         emit(rmc::pred::OP_HALT, 0, 0);
     }
@@ -438,7 +463,7 @@ private:
         const std::vector<Tok> toks = tokenize(*u, true);
         PNodeP body;
         try {
-            body = PredParser(toks).parse_all();
+            body = PredParser(toks, actions).parse_all();
         } catch (PredError& e) {
             e.msg = "in " + name + ": " + e.msg;
             throw;
@@ -466,8 +491,20 @@ private:
 
     static bool is_id(const PNodeP& n, const char* s) { return n->kind == PNode::ID && n->s == s; }
     // log[i]: the server expression, or null
-    static PNodeP log_of(const PNodeP& n) {
-        return n->kind == PNode::INDEX && is_id(n->k[0], "log") ? n->k[1] : nullptr;
+    // (*pr: the variable is primed, log'[i])
+    PNodeP log_of(const PNodeP& n, bool* pr) const {
+        if (n->kind != PNode::INDEX) return nullptr;
+        const PNodeP v = var_of(n->k[0], pr);
+        return is_id(v, "log") ? n->k[1] : nullptr;
+    }
+    // a variable as written, x or x': the ID, and whether it is primed (a prime inside a primed
+    // expression is refused)
+    PNodeP var_of(const PNodeP& n, bool* pr) const {
+        *pr = false;
+        if (n->kind != PNode::PRIME || n->k[0]->kind != PNode::ID) return n;
+        if (primed) refuse("a prime inside an already primed expression", n);
+        *pr = true;
+        return n->k[0];
     }
     // through a parameter to the argument it stands for (so Len(l) with l <- log[i] reads as written out)
     PNodeP resolve(PNodeP n, const PEnv*& env) const {
@@ -485,6 +522,7 @@ private:
     struct Domain {
         Op iter, next;
         PTy ty;
+        bool bagp = false;  // T_MSG: the slots are of the successor's bag
     };
     // the code that sets up a quantifier's domain (left on the stack for the ITER instruction)
     Domain gen_domain(const PNodeP& d0, const PEnv& env0) {
@@ -510,17 +548,18 @@ private:
         if (d->kind == PNode::DOMAIN) {
             const PEnv* e2 = &env;
             const PNodeP x = resolve(d->k[0], e2);
-            if (is_id(x, "messages")) {
+            bool pr = false;
+            if (is_id(var_of(x, &pr), "messages")) {
                 emit(OP_PUSH, 0, 1);
-                emit(OP_NMSG, 0, 1);
+                emit(rd(OP_NMSG, primed || pr), 0, 1);
                 emit(OP_PUSH, 1, 1);
                 emit(OP_SUB, 0, -1);
-                return {OP_ITER_RANGE, OP_NEXT_RANGE, T_MSG};
+                return {OP_ITER_RANGE, OP_NEXT_RANGE, T_MSG, primed || pr};
             }
-            if (PNodeP i = log_of(x)) {
+            if (PNodeP i = log_of(x, &pr)) {
                 emit(OP_PUSH, 1, 1);
                 gen_server(i, *e2, "the index of log");
-                emit(OP_LEN, 0, 0);
+                emit(rd(OP_LEN, primed || pr), 0, 0);
                 return {OP_ITER_RANGE, OP_NEXT_RANGE, T_INT};
             }
             refuse("DOMAIN of anything but messages or log[i]", d);
@@ -549,6 +588,7 @@ private:
         PBinding b;
         b.reg = r;
         b.ty = dm.ty;
+        b.bagp = dm.bagp;
         inner.m[n->names[k]] = b;
         gen_quant(n, inner, k + 1);
         emit(all ? OP_JT : OP_JF, loop, -1);  // \A: a true body goes on; \E: a false one
@@ -581,11 +621,12 @@ private:
         if (r->kind == PNode::DOMAIN) {
             const PEnv* e2 = envp;
             const PNodeP x = resolve(r->k[0], e2);
-            if (PNodeP i = log_of(x)) {
+            bool pr = false;
+            if (PNodeP i = log_of(x, &pr)) {
                 want(gen(n->k[0], env), T_INT, n->k[0], "the left of \\in DOMAIN log[i]");
                 emit(OP_PUSH, 1, 1);
                 gen_server(i, *e2, "the index of log");
-                emit(OP_LEN, 0, 0);
+                emit(rd(OP_LEN, primed || pr), 0, 0);
                 emit(OP_INRANGE, 0, -2);
                 return T_BOOL;
             }
@@ -656,6 +697,7 @@ private:
         if (const PBinding* b = env.find(s)) {
             if (b->reg >= 0) {
                 emit(OP_LOAD, b->reg, 1);
+                msg_bagp = b->bagp;
                 return b->ty;
             }
             return gen(b->arg, *b->env);
@@ -771,6 +813,11 @@ private:
             case PNode::INDEX: return gen_index(n, env);
             case PNode::FIELD: return gen_field(n, env);
             case PNode::CALL: return gen_call(n, env);
+            case PNode::PRIME: {
+                if (primed) refuse("a prime inside an already primed expression", n);
+                PrimeScope ps(*this, true);
+                return gen(n->k[0], env);
+            }
         }
         refuse("this construct", n);
     }
@@ -778,7 +825,9 @@ private:
     PTy gen_index(const PNodeP& n, const PEnv& env0) {
         using namespace rmc::pred;
         const PEnv* envp = &env0;
-        const PNodeP base = resolve(n->k[0], envp);
+        bool pr = false;
+        const PNodeP base = var_of(resolve(n->k[0], envp), &pr);
+        const bool nx = primed || pr;
         static const std::map<std::string, std::pair<Op, PTy>> vars = {
             {"currentTerm", {OP_TERM, T_INT}}, {"state", {OP_ROLE, T_ROLE}}, {"votedFor", {OP_VOTED, T_SERVER}},
             {"commitIndex", {OP_COMMIT, T_INT}}, {"votesResponded", {OP_VRESP, T_SET}},
@@ -787,12 +836,16 @@ private:
             auto it = vars.find(base->s);
             if (it != vars.end()) {
                 gen_server(n->k[1], env0, ("the index of " + base->s).c_str());
-                emit(it->second.first, 0, 0);
+                emit(rd(it->second.first, nx), 0, 0);
                 return it->second.second;
             }
             if (base->s == "messages") {
                 want(gen(n->k[1], env0), T_MSG, n->k[1], "the index of messages");
-                emit(OP_MSGCNT, 0, 0);
+                if (msg_bagp != nx)
+                    refuse(std::string("a message bound in ") + (msg_bagp ? "DOMAIN messages'" : "DOMAIN messages") +
+                           " as an index of " + (nx ? "messages'" : "messages") + " (a bound message is a slot of the bag "
+                           "it was bound in)", n);
+                emit(rd(OP_MSGCNT, nx), 0, 0);
                 return T_INT;
             }
             if (base->s == "log")
@@ -803,11 +856,12 @@ private:
         }
         if (base->kind == PNode::INDEX) {
             const PEnv* e2 = envp;
-            const PNodeP bb = resolve(base->k[0], e2);
+            bool pr2 = false;
+            const PNodeP bb = var_of(resolve(base->k[0], e2), &pr2);
             if (is_id(bb, "nextIndex") || is_id(bb, "matchIndex")) {
                 gen_server(base->k[1], *envp, "the first index");
                 gen_server(n->k[1], env0, "the second index");
-                emit(is_id(bb, "nextIndex") ? OP_NEXT : OP_MATCH, 0, -1);
+                emit(rd(is_id(bb, "nextIndex") ? OP_NEXT : OP_MATCH, primed || pr2), 0, -1);
                 return T_INT;
             }
             if (is_id(bb, "log"))
@@ -823,11 +877,12 @@ private:
         if (base->kind == PNode::INDEX) {  // log[i][n].term / .value
             const PEnv* e2 = envp;
             const PNodeP inner = resolve(base->k[0], e2);
-            if (PNodeP i = log_of(inner)) {
+            bool pr = false;
+            if (PNodeP i = log_of(inner, &pr)) {
                 if (n->s != "term" && n->s != "value") refuse("field ." + n->s + " of a log entry (term, value)", n);
                 gen_server(i, *e2, "the index of log");
                 want(gen(base->k[1], *envp), T_INT, base->k[1], "the position in log[i]");
-                emit(n->s == "term" ? OP_LOGTERM : OP_LOGVAL, 0, -1);
+                emit(rd(n->s == "term" ? OP_LOGTERM : OP_LOGVAL, primed || pr), 0, -1);
                 return n->s == "term" ? T_INT : T_VALUE;
             }
         }
@@ -843,7 +898,7 @@ private:
         if (it == fields.end()) refuse("field ." + n->s, n);
         const PTy t = gen(n->k[0], env0);
         if (t != T_MSG) refuse(std::string("field .") + n->s + " of a " + ty_name(t), n);
-        emit(OP_MSGF, it->second.first, 0);
+        emit(rd(OP_MSGF, msg_bagp), it->second.first, 0);  // (the bag it was bound in, primed or not here)
         return it->second.second;
     }
 
@@ -854,10 +909,11 @@ private:
             if (n->k.size() != 1) refuse(f + " takes one argument", n);
             const PEnv* e2 = &env;
             const PNodeP x = resolve(n->k[0], e2);
-            PNodeP i = log_of(x);
+            bool pr = false;
+            PNodeP i = log_of(x, &pr);
             if (!i) refuse(f + " of anything but log[i]", n);
             gen_server(i, *e2, "the index of log");
-            emit(f == "Len" ? OP_LEN : OP_LASTTERM, 0, 0);
+            emit(rd(f == "Len" ? OP_LEN : OP_LASTTERM, primed || pr), 0, 0);
             return T_INT;
         }
         if (f == "Cardinality") {
@@ -866,8 +922,9 @@ private:
             const PNodeP x = resolve(n->k[0], e2);
             if (x->kind == PNode::DOMAIN) {
                 const PEnv* e3 = e2;
-                if (is_id(resolve(x->k[0], e3), "messages")) {
-                    emit(OP_NMSG, 0, 1);
+                bool pr = false;
+                if (is_id(var_of(resolve(x->k[0], e3), &pr), "messages")) {
+                    emit(rd(OP_NMSG, primed || pr), 0, 1);
                     return T_INT;
                 }
             }
@@ -904,16 +961,23 @@ struct Residual {
 // line and column.  what: "model-defined invariants" / "residual constraint conjuncts".
 inline bool compile_program(const Ctx& X, const std::vector<PredItem>& items, const char* what,
                             const std::vector<std::string>& servers, const std::vector<std::string>& values,
-                            rmc_predicates* out, std::string* err) {
+                            rmc_predicates* out, std::string* err, bool actions = false) {
     using namespace rmc::pred;
     memset(out, 0, sizeof *out);
     out->prog.n_servers = (int)servers.size();
+    out->actions = actions ? 1 : 0;
+    if (actions && (int)items.size() > RMC_MAX_ACTION_PROPS) {
+        *err = std::to_string(items.size()) + " " + what + " exceed RMC_MAX_ACTION_PROPS = " +
+               std::to_string(RMC_MAX_ACTION_PROPS);
+        return false;
+    }
     if ((int)items.size() > PRED_MAX) {
         *err = std::to_string(items.size()) + " " + what + " exceed RMC_MAX_PREDICATES = " + std::to_string(PRED_MAX);
         return false;
     }
     std::vector<uint32_t> code;
     PredGen g(X, servers, values, code);
+    g.set_actions(actions);
     for (size_t p = 0; p < items.size(); ++p) {
         const std::string& label = items[p].label;
         out->prog.entry[p] = (int)code.size();
@@ -953,6 +1017,20 @@ inline bool compile_predicates(const Ctx& X, const std::vector<std::string>& nam
     std::vector<PredItem> items;
     for (const auto& n : names) items.push_back({n, "INVARIANT " + n, nullptr});
     return compile_program(X, items, "model-defined invariants", servers, values, out, err);
+}
+
+// An action property of the cfg (PROPERTY P with P == [][A]_vars): its name and A's tokens.
+struct ActionProp {
+    std::string name;
+    std::vector<Tok> toks;
+};
+
+// The model's action properties, in cfg order: each A with primes in the language.
+inline bool compile_actions(const Ctx& X, const std::vector<ActionProp>& props, const std::vector<std::string>& servers,
+                            const std::vector<std::string>& values, rmc_predicates* out, std::string* err) {
+    std::vector<PredItem> items;
+    for (const auto& a : props) items.push_back({a.name, "PROPERTY " + a.name, &a.toks});
+    return compile_program(X, items, "action properties", servers, values, out, err, true);
 }
 
 // The residual conjuncts of the model's CONSTRAINTs, in order.

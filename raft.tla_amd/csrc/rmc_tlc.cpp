@@ -440,6 +440,9 @@ int main(int argc, char** argv) {
     // CONSTRAINT conjuncts that are none of the four bounds (residuals) are compiled the same way
     // and filter what the single-GPU search stores, in a pass after each of its launches
     fopts |= RMC_FRONT_CONSTRAINTS;
+    // a PROPERTY of the form [][A]_vars is an action property: compiled the same way, with primes,
+    // and checked on every transition by a pass of the single-GPU search
+    fopts |= RMC_FRONT_ACTIONS;
     if (depth > 0 && !simulate) fopts |= RMC_FRONT_DEPTH_BOUNDED;
     rmc_predicates* preds = nullptr;
     {
@@ -460,6 +463,28 @@ int main(int argc, char** argv) {
             rmc_predicates_free(preds);
             return 1;
         }
+    }
+    rmc_predicates* acts = nullptr;
+    {
+        char aerr[2048];
+        if (rmc_actions_from_files(cfg.c_str(), tla.c_str(), raft.empty() ? nullptr : raft.c_str(),
+                                   fopts | (simulate ? RMC_FRONT_SIMULATE : 0u), &acts, aerr, sizeof aerr)) {
+            printf("Error: %s\n", aerr);
+            rmc_predicates_free(preds);
+            rmc_predicates_free(cons);
+            return 1;
+        }
+    }
+    const int nacts = rmc_predicates_count(acts);
+    if (nacts && (cont || gpus > 1 || simulate || !ckpt.empty() || !recover.empty() || rmc_predicates_count(cons))) {
+        printf("Error: PROPERTY %s is an action property, checked by the single-GPU search's pass over every "
+               "transition: not with %s\n", rmc_predicates_name(acts, 0),
+               cont ? "-continue" : gpus > 1 ? "-gpus N > 1" : simulate ? "-simulate" : !ckpt.empty() ? "-checkpoint"
+               : !recover.empty() ? "-recover" : "a CONSTRAINT conjunct that is no bound");
+        rmc_predicates_free(preds);
+        rmc_predicates_free(cons);
+        rmc_predicates_free(acts);
+        return 1;
     }
     const int ncons = rmc_predicates_count(cons);
     if (ncons && (verify || cont || coverage || !dump.empty() || gpus > 1 || simulate || !ckpt.empty() || !recover.empty())) {
@@ -544,6 +569,16 @@ int main(int argc, char** argv) {
         }
         printf("Compiled model-defined invariants:");
         for (int p = 0; p < npred; ++p) printf("%s %s", p ? "," : "", rmc_predicates_name(preds, p));
+        printf("\n");
+    }
+    if (nacts) {
+        if (rmc_set_actions(ctx, acts)) {
+            printf("Error: %s\n", rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 1;
+        }
+        printf("Compiled action properties:");
+        for (int p = 0; p < nacts; ++p) printf("%s %s", p ? "," : "", rmc_predicates_name(acts, p));
         printf("\n");
     }
     if (ncons) {
@@ -699,7 +734,17 @@ int main(int argc, char** argv) {
         print_behaviour();
         exitcode = 12;
     } else if (r.violated_inv || r.deadlock) {
-        if ((uint32_t)r.violated_inv >= RMC_INV_USER0) {  // a model-defined invariant: bit 16 + p
+        if ((uint32_t)r.violated_inv >= RMC_ACT_USER0) {  // an action property: bit 24 + p
+            int32_t prop = 0, is_err = 0;
+            rmc_action_violation(ctx, &prop, nullptr, nullptr, nullptr, &is_err);
+            const char* name = rmc_predicates_name(acts, prop);
+            if (is_err)
+                printf("Error: Evaluating action property %s failed: a read outside its domain (log[i][n] beyond "
+                       "Len(log[i]), a server index that is Nil, or a field of another message type).\n",
+                       name ? name : "?");
+            else
+                printf("Error: Action property %s is violated.\n", name ? name : "?");
+        } else if ((uint32_t)r.violated_inv >= RMC_INV_USER0) {  // a model-defined invariant: bit 16 + p
             const char* name = rmc_predicates_name(preds, __builtin_ctz((uint32_t)r.violated_inv) - 16);
             if (rmc_predicate_error(ctx))
                 printf("Error: Evaluating invariant %s failed: a read outside its domain (log[i][n] beyond "
@@ -766,5 +811,6 @@ int main(int argc, char** argv) {
     rmc_destroy(ctx);
     rmc_predicates_free(preds);
     rmc_predicates_free(cons);
+    rmc_predicates_free(acts);
     return exitcode;
 }

@@ -33,6 +33,9 @@ INV_NAMES = {INV_TYPEOK: "TypeOK", INV_ONE_LEADER: "OneLeaderPerTerm",
              INV_MORE_UP_TO_DATE: "MoreUpToDateCorrect", INV_LEADER_COMPLETE: "LeaderCompleteness"}
 FRONT_BUILTIN_RAFT, FRONT_SIMULATE, FRONT_DEPTH_BOUNDED, FRONT_PREDICATES = 1, 2, 4, 8
 FRONT_CONSTRAINTS = 16   # RMC_FRONT_CONSTRAINTS: CONSTRAINT conjuncts that are no bound become residuals
+FRONT_ACTIONS = 32       # RMC_FRONT_ACTIONS: a PROPERTY [][A]_vars is an action property
+ACT_USER0 = 1 << 24      # RMC_ACT_USER0: action property p is bit 24 + p of Result.violated_inv
+MAX_ACTION_PROPS = 4
 MAX_PREDICATES = 8       # RMC_MAX_PREDICATES: model-defined invariants per program
 INV_USER0 = 1 << 16      # RMC_INV_USER0: predicate p is bit 16 + p of Result.violated_inv
 PRED_HOLDS, PRED_VIOLATED, PRED_ERROR = 0, 1, 2  # verdicts of rmc_eval_predicates
@@ -163,7 +166,8 @@ EXPORTS = ("rmc_create", "rmc_destroy", "rmc_last_error", "rmc_version", "rmc_ru
            "rmc_get_levels", "rmc_read_states", "rmc_find_states", "rmc_graph_edges",
            "rmc_predicates_from_files", "rmc_predicates_free", "rmc_predicates_count", "rmc_predicates_name",
            "rmc_set_predicates", "rmc_eval_predicates", "rmc_predicate_error",
-           "rmc_constraints_from_files", "rmc_set_constraints", "rmc_constraint_error")
+           "rmc_constraints_from_files", "rmc_set_constraints", "rmc_constraint_error",
+           "rmc_actions_from_files", "rmc_set_actions", "rmc_eval_actions", "rmc_action_violation")
 
 _lib = None
 
@@ -276,6 +280,16 @@ def native():
         lib.rmc_constraints_from_files.restype = C.c_int
         lib.rmc_set_constraints.argtypes = [C.c_void_p, C.c_void_p]
         lib.rmc_set_constraints.restype = C.c_int
+        lib.rmc_actions_from_files.argtypes = lib.rmc_predicates_from_files.argtypes
+        lib.rmc_actions_from_files.restype = C.c_int
+        lib.rmc_set_actions.argtypes = [C.c_void_p, C.c_void_p]
+        lib.rmc_set_actions.restype = C.c_int
+        lib.rmc_eval_actions.argtypes = [C.c_void_p, C.POINTER(StateView), C.POINTER(StateView), C.c_size_t,
+                                         C.POINTER(C.c_uint8)]
+        lib.rmc_eval_actions.restype = C.c_int
+        lib.rmc_action_violation.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.rmc_action_violation.restype = C.c_int
         lib.rmc_constraint_error.argtypes = [C.c_void_p]
         lib.rmc_constraint_error.restype = C.c_int
         _lib = lib
@@ -345,25 +359,43 @@ class Constraints(Predicates):
     _from_files = "rmc_constraints_from_files"
 
 
+class Actions(Predicates):
+    """The action properties of a model, compiled (rmc_actions_from_files): the PROPERTY names
+    of its .cfg whose definition is [][A]_vars, in cfg order.  Property p is bit
+    ACT_USER0 << p of Result.violated_inv.  Empty: the model has none."""
+    _from_files = "rmc_actions_from_files"
+
+    def name_of(self, violated_inv):
+        for p, name in enumerate(self.names):
+            if violated_inv == ACT_USER0 << p:
+                return name
+        return None
+
+
 def load_model(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, depth_bounded=False, predicates=False,
-               constraints=False):
+               constraints=False, actions=False):
     """(Config, provenance notes, Predicates or None): rmc_model_from_files for a BFS model;
     predicates=True accepts INVARIANTs of the model's own (RMC_FRONT_PREDICATES) and
     compiles them — hand them to Checker.set_predicates.  constraints=True accepts
     CONSTRAINT conjuncts that are no bound (RMC_FRONT_CONSTRAINTS), compiles them, and
-    returns a fourth value, the Constraints — hand them to Checker.set_constraints."""
+    returns a fourth value, the Constraints — hand them to Checker.set_constraints.
+    actions=True accepts PROPERTY names of the form [][A]_vars (RMC_FRONT_ACTIONS), compiles
+    them, and returns the Actions as one more, last value — hand them to Checker.set_actions."""
     cfg, _sc, notes = model_from_files(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded=depth_bounded,
-                                       predicates=predicates, constraints=constraints)
-    more = FRONT_CONSTRAINTS if constraints else 0
-    preds = Predicates(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, more) if predicates else None
-    if not constraints:
-        return cfg, notes, preds
-    more = FRONT_PREDICATES if predicates else 0
-    return cfg, notes, preds, Constraints(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, more)
+                                       predicates=predicates, constraints=constraints, actions=actions)
+    every = (FRONT_CONSTRAINTS if constraints else 0) | (FRONT_PREDICATES if predicates else 0) | \
+        (FRONT_ACTIONS if actions else 0)
+    preds = Predicates(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, every) if predicates else None
+    out = [cfg, notes, preds]
+    if constraints:
+        out.append(Constraints(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, every))
+    if actions:
+        out.append(Actions(cfg_path, tla_path, raft_path, builtin_raft, depth_bounded, every))
+    return tuple(out)
 
 
 def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False, simulate=False,
-                     depth_bounded=False, predicates=False, constraints=False):
+                     depth_bounded=False, predicates=False, constraints=False, actions=False):
     """rmc_model_from_files: (Config, SimConfig or None, provenance notes).
     Raises RmcError naming the construct when the model is not the compiled-in
     raft.tla (with its recognised bug variant, bounds and invariants).
@@ -374,7 +406,7 @@ def model_from_files(cfg_path, tla_path=None, raft_path=None, builtin_raft=False
     info = C.create_string_buffer(4096)
     opts = (FRONT_BUILTIN_RAFT if builtin_raft else 0) | (FRONT_SIMULATE if simulate else 0) | \
         (FRONT_DEPTH_BOUNDED if depth_bounded else 0) | (FRONT_PREDICATES if predicates else 0) | \
-        (FRONT_CONSTRAINTS if constraints else 0)
+        (FRONT_CONSTRAINTS if constraints else 0) | (FRONT_ACTIONS if actions else 0)
     rc = lib.rmc_model_from_files(cfg_path.encode(), tla_path.encode() if tla_path else None,
                                   raft_path.encode() if raft_path else None, opts, C.byref(cfg),
                                   C.byref(sc) if simulate else None, info, 4096)
@@ -646,6 +678,35 @@ class Checker:
     def constraint_error(self):
         """rmc_constraint_error: 1 + the residual whose evaluation error stopped run(), else 0."""
         return self.lib.rmc_constraint_error(self.ctx)
+
+    # ---- action properties (rmc.h "action properties") ----
+    def set_actions(self, acts):
+        """rmc_set_actions: run() then checks the compiled action properties (an Actions) on
+        every transition; None removes them.  The ctx keeps its own copy."""
+        self._check(self.lib.rmc_set_actions(self.ctx, acts.handle if acts is not None else None))
+        self._act_names = list(acts.names) if acts is not None else []
+
+    def eval_actions(self, pairs):
+        """rmc_eval_actions: per pair (current StateView, next StateView) the verdict of every
+        property, in order (PRED_HOLDS, PRED_VIOLATED, PRED_ERROR), by the device interpreter,
+        with the stutter rule applied."""
+        cur = (StateView * len(pairs))(*[p[0] for p in pairs])
+        nxt = (StateView * len(pairs))(*[p[1] for p in pairs])
+        np_ = len(getattr(self, "_act_names", []))
+        out = (C.c_uint8 * max(1, len(pairs) * np_))()
+        self._check(self.lib.rmc_eval_actions(self.ctx, cur, nxt, len(pairs), out))
+        return [tuple(out[t * np_:(t + 1) * np_]) for t in range(len(pairs))]
+
+    def action_violation(self):
+        """rmc_action_violation: the transition run() reported, as a dict (property, name,
+        src_index, family, instance, is_error); RmcError(E_STATE) when it reported none."""
+        prop, fam, inst, err = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        src = C.c_uint64()
+        self._check(self.lib.rmc_action_violation(self.ctx, C.byref(prop), C.byref(src), C.byref(fam), C.byref(inst),
+                                                  C.byref(err)))
+        names = getattr(self, "_act_names", [])
+        return {"property": prop.value, "name": names[prop.value] if prop.value < len(names) else None,
+                "src_index": src.value, "family": fam.value, "instance": inst.value, "is_error": bool(err.value)}
 
     # ---- the state graph of the last completed run() (rmc.h "state graph export") ----
     def levels(self):

@@ -88,12 +88,21 @@ public:
         return n;
     }
 
+    // TLA+'s levels: => (1) binds looser than <=> (2), so `a <=> b => c` is `(a <=> b) => c` and
+    // `a => b <=> c` is `a => (b <=> c)`; neither chains with itself
     PNodeP expr() {
-        PNodeP a = disj();
-        if (is_any({"=>", "<=>", "\\equiv"})) {
+        PNodeP a = equiv();
+        if (is("=>")) {
             const Tok op = v[i++];
-            PNodeP b = disj();
-            return bin(op, op.t == "=>" ? "=>" : "<=>", a, b);
+            return bin(op, "=>", a, equiv());
+        }
+        return a;
+    }
+    PNodeP equiv() {
+        PNodeP a = disj();
+        if (is_any({"<=>", "\\equiv"})) {
+            const Tok op = v[i++];
+            return bin(op, "<=>", a, disj());
         }
         return a;
     }
